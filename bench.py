@@ -24,7 +24,11 @@ At N = 1 the line also carries `ladder` (the metric's 26 x 26 ... 416 x 416 grid
 and roofline fraction per size, the CPU oracle's forward year beside it), `roofline_precond` (the
 one genuinely HBM-streaming kernel) and `cpu_baseline`.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed Krylov iteration.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last of them handed the caller of the solve -- its
+increment, per tracer module -- as DIR/increment_<module>.npy (float64).  Inputs depend on the arguments only, so two
+builds can be compared output for output.
 """
 
 import argparse
@@ -222,7 +226,8 @@ class Workload:
         solverinfo["krylov_max_iter"] = str(k_iters)
         solver = nkdist.DistributedKrylovSolver(self.iterate, solverinfo, resume=False, rewind=False,
                                                 hist_fname=None, device=device)
-        solver.solve(os.path.join(self.workdir, f"increment_{tag}.nc"), self.fcn)
+        # what a caller of the solve receives: the Newton increment of its last iteration (--dump-outputs)
+        self.increment = solver.solve(os.path.join(self.workdir, f"increment_{tag}.nc"), self.fcn)
         return solver
 
     def close(self):
@@ -230,6 +235,28 @@ class Workload:
 
         ModelState.reset_class()
         shutil.rmtree(self.workdir, ignore_errors=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, increment):
+    """--dump-outputs: what the timed Krylov solve handed its caller -- the increment of its last iteration, one float64
+    array (tracers, depth, ypos) per tracer module -- as out_dir/increment_<module>.npy.  Above 64 MB in all, every array
+    is cut to a sample of its flattened elements drawn by a generator of fixed seed (the same sample for the same grid)."""
+    import numpy as np
+
+    arrays = {f"increment_{tms.name}": np.ascontiguousarray(tms.get_tracer_vals_all(), dtype=np.float64)
+              for tms in increment.tracer_modules}
+    total = sum(arr.nbytes for arr in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)       # (room for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        if total > budget:
+            keep = arr.size * budget // total
+            arr = arr.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, arr.size, keep))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    return sorted(arrays)
 
 
 MIX_NAMES = ["iage", "phosphorus", "forced_dye"]
@@ -762,6 +789,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=4,
                     help="untimed Krylov iterations (then as many more as the allocation of a large grid's schedule cache takes, "
                          "config.untimed_iterations_until_the_schedule_cache_was_allocated)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the increment of the Krylov solve) "
+                         "as DIR/<name>.npy (rank 0)")
     ap.add_argument("--grid", type=int, default=416, help="depth and ypos levels")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=25.0)
     ap.add_argument("--no-files", action="store_true", help="skip the NetCDF trail (not the default)")
@@ -784,6 +814,8 @@ def main():
                     help="only start the ranks, all-reduce their ranks over gloo and print the world size "
                          "(CPU check of the self-launch path, tests/test_dist.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed Krylov iteration")
     if os.environ.get("NK2D_BENCH_DEBUG"):
         # stacks of every thread on stderr should a leg hang (seconds)
         import faulthandler
@@ -861,6 +893,9 @@ def main():
         if world > 1:
             torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(el.item())
+        if args.dump_outputs and rank == 0:
+            names = dump_outputs(args.dump_outputs, wl.increment)
+            progress(f"outputs of the last timed step: {', '.join(names)} in {args.dump_outputs}")
         from nk_ooc_amd.model_state import ModelState
 
         jvp_stats = ModelState.last_stats[0]

@@ -1,8 +1,7 @@
 """Stand-ins for the three I/O-only third-party modules the reference imports and this image lacks
 (netCDF4, xarray, pint), so that the reference's OWN solver classes can run in the build container
 ("shim plan").  TEST INFRASTRUCTURE: used by tests/golden/gen_ref_traces.py (which
-makes the G7 / G8 fixtures with nk_ooc.krylov_solver / nk_ooc.newton_solver themselves) and by
-tests/test_ref_dropin.py (the real nk_ooc.nk_driver driving this repository's plugin).  Nothing here is
+makes the G7 / G8 fixtures with nk_ooc.krylov_solver / nk_ooc.newton_solver themselves).  Nothing here is
 on the arithmetic path: the reference uses these modules for files, for the per-module container of
 tracer arrays and for unit strings.
 

@@ -15,5 +15,5 @@ kernels are re-routed:
 * `iage.apply_precond_jacobian` (`nk_ooc/py_driver_2d/iage.py:66-93`)   -> `nk2d_precond_apply`
 
 The package is installed by making it visible on `nk_ooc.__path__` (or by copying it into the reference
-tree).  `tests/test_ref_dropin.py` runs the reference's real driver against it in the build container.
+tree).  `tests/test_gpu_capi_krylov.py` checks its HIP side.
 """

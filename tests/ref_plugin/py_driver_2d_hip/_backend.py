@@ -1,8 +1,7 @@
 """Binding of the plugin to libnk2d.so (C ABI of include/nk2d.h through this repository's ctypes layer).
 
 `HipBackend` is the product path: it needs the built library and a GPU and fails loudly otherwise.  A test
-harness without a GPU may install a stand-in with `set_backend` (tests/test_ref_dropin.py checks the plugin's
-plumbing under the reference's real driver that way); nothing in this package falls back by itself."""
+harness without a GPU may install a stand-in with `set_backend`; nothing in this package falls back by itself."""
 import numpy as np
 
 _BACKEND = None

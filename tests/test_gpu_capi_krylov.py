@@ -245,8 +245,7 @@ def test_norm_hook_couples_two_single_tracer_engines():
 
 def test_plugin_backend_on_the_device():
     """the HIP side of the variant-B plugin (tests/ref_plugin/py_driver_2d_hip/_backend.py) without the reference
-    around it: what it hands the reference's comp_fcn in place of solve_ivp's result, and the preconditioner.
-    (The reference side of the same plugin runs under the real nk_driver in tests/test_ref_dropin.py.)"""
+    around it: what it hands the reference's comp_fcn in place of solve_ivp's result, and the preconditioner."""
     import sys
     import types
 
