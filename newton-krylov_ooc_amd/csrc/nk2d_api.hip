@@ -182,6 +182,11 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
     if (key == "frozen_cache_after") { c->frozen_cache_after = (int)value; return 0; }
     if (key == "spec_bias") { c->spec_bias = value > 0.0 ? value : 1.0; return 0; }
     if (key == "stream_years") { c->stream_years = (int)value; c->stream_lost = 0; return 0; }
+    if (key == "frozen_tape") {
+        if (value != 0.0 && value != 1.0) return nk2d_fail(c, "nk2d_set_option: frozen_tape is 0 or 1");
+        c->frozen_tape = (int)value;
+        return 0;
+    }
     if (key == "stream_two_waves") {
         // (decides the shape of the resident kernel: taken before the context's first year as a command stream)
         if (c->strm) return nk2d_fail(c, "nk2d_set_option: stream_two_waves must be set before the first year of the context");
@@ -557,6 +562,10 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->stream_on = 0;
     c->stream_lost = 0;
     c->stream_cmds = c->stream_launches = c->stream_timeouts = c->stream_years_run = 0;
+    c->frozen_tape = 0;
+    c->tape = nullptr;
+    c->tape_rec = c->tape_foreign = 0;
+    c->tape_years_run = c->tape_builds = c->tape_timeouts = c->tape_fallbacks = 0;
     c->frozen_wpb = 2;
     c->frozen_alloc_async = 1;
     c->barrier_timeout_ms = 2000.0;
@@ -771,6 +780,7 @@ extern "C" int nk2d_set_region(nk2d_ctx* c, const int32_t* mask, const double* w
     NK2D_CHECK(c, hipGetLastError());
     if (nreg != c->nreg) {
         NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+        nk2d_tape_forget(c);     // (the commands of a recorded frozen year write norm partials to PART)
         NK2D_CHECK(c, hipFree(c->PART));
         c->PART = nullptr;
         NK2D_TRY(dev_alloc(c, &c->PART, (size_t)c->ncol * nreg));
@@ -1051,6 +1061,12 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "stream_timeouts") v = c->stream_timeouts;
     else if (key == "stream_columns_per_workgroup") v = nk2d_stream_columns_per_workgroup(c);
     else if (key == "stream_two_waves_kernel") v = nk2d_stream_two_waves(c);
+    else if (key == "tape_years_run") v = c->tape_years_run;
+    else if (key == "tape_builds") v = c->tape_builds;
+    else if (key == "tape_timeouts") v = c->tape_timeouts;
+    else if (key == "tape_fallbacks") v = c->tape_fallbacks;
+    else if (key == "tape_bytes") v = nk2d_tape_size(c, 0);
+    else if (key == "tape_commands") v = nk2d_tape_size(c, 1);
     else if (key.rfind("stream_prof_", 0) == 0) {
         // stream_prof_0 .. stream_prof_11: see nk2d_stream_profile
         double pr[12];

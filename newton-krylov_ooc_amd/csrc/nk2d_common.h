@@ -49,6 +49,13 @@ struct nk2d_ctx {
     int stream_on;         // set by the integrator for the span of a year that may run as a command stream
     int stream_lost;       // years in a row whose kernel gave up (two: the context stops trying)
     int64_t stream_cmds, stream_launches, stream_timeouts, stream_years_run;   // counters (nk2d_get_counter)
+    // a frozen year replayed from a command tape in HBM (option "frozen_tape", nk2d_stream.h): recorded once per schedule
+    // (tape_rec: nk2d_stream_push appends to the tape, nothing runs; tape_foreign counts launches that have no command)
+    int frozen_tape;
+    struct nk2d_tape* tape;
+    int tape_rec, tape_foreign;
+    int64_t tape_years_run, tape_builds, tape_timeouts;   // counters (nk2d_get_counter)
+    int64_t tape_fallbacks;   // ... and taped years handed to the existing path without a timeout (not resident, refused recording)
 
     // static, packed planes (device)
     double* VV;      // vvel at ypos faces, (ny+1) columns
@@ -260,6 +267,8 @@ int nk2d_stream_eligible(const nk2d_ctx* c);
 int nk2d_stream_ready(nk2d_ctx* c);     // buffers of the command stream in place (first use)
 int nk2d_stream_end(nk2d_ctx* c);       // ends the kernel, waits for it; NK2D_RC_STREAM_LOST if it had given up on the way
 void nk2d_stream_free(nk2d_ctx* c);
+int64_t nk2d_tape_size(const nk2d_ctx* c, int what);   // the current tape: 0 bytes, 1 commands
+void nk2d_tape_forget(nk2d_ctx* c);   // a buffer a recorded command may point at is reallocated: the tape is recorded again
 int nk2d_stream_profile(nk2d_ctx* c, double* out12);
 double* nk2d_stream_part_take(nk2d_ctx* c, const double* name);
 const double* nk2d_stream_part_named(const nk2d_ctx* c, const double* name);
@@ -269,6 +278,7 @@ int nk2d_stream_wait_part(nk2d_ctx* c, const double* part, int n);
 // commands pushed so far, so a resident command-stream kernel is told to finish first (the caller's launch is then ordered
 // behind it by the stream; nothing is waited for here)
 static inline hipStream_t nk2d_s(nk2d_ctx* c) {
+    if (c->tape_rec) c->tape_foreign++;     // (recording a tape: this launch would run now, not in its place on the tape)
     if (c->strm && nk2d_stream_running(c)) (void)nk2d_stream_pause(c);
     return c->stream_;
 }
@@ -611,6 +621,7 @@ int nk2d_r_newton_final(nk2d_ctx* c, bool do_stage, bool first, double mreal, do
 int nk2d_r_attempt_setup(nk2d_ctx* c, const double* times, double* const* out, double x0, double x1, double x2,
                          int jac_stage = -1);
 double nk2d_fingerprint(const nk2d_ctx* c);
+uint64_t nk2d_frozen_key(const nk2d_ctx* c, const double* sched, int64_t n);   // schedule ^ fingerprint ^ frozen_err_check
 int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vector<char>* err_rows = nullptr);
 int nk2d_frozen_cache_pending(const nk2d_ctx* c);
 int64_t nk2d_frozen_cache_bytes(const nk2d_ctx* c);

@@ -346,6 +346,12 @@ static uint64_t sched_key(const double* sched, int64_t n) {
     return h ? h : 1;
 }
 
+// what a schedule cache (and a command tape, option "frozen_tape") is kept for: the schedule, the context's fingerprint and the
+// error-estimate stride
+uint64_t nk2d_frozen_key(const nk2d_ctx* c, const double* sched, int64_t n) {
+    return sched_key(sched, n) ^ (uint64_t)nk2d_fingerprint(c) ^ ((uint64_t)(c->frozen_err_check + 1) * 0x9E3779B97F4A7C15ull);
+}
+
 // 1 while a thread is allocating the slab of this context's schedule cache
 int nk2d_frozen_cache_pending(const nk2d_ctx* c) {
     const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
@@ -523,7 +529,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     nk2d_frozen_cache* fc = (nk2d_frozen_cache*)c->frozen_cache;
     if (!fc) { fc = new nk2d_frozen_cache(); c->frozen_cache = fc; }
     // (the rows also say which steps carry an error estimate)
-    const uint64_t key = sched_key(sched, n) ^ (uint64_t)nk2d_fingerprint(c) ^ ((uint64_t)(c->frozen_err_check + 1) * 0x9E3779B97F4A7C15ull);
+    const uint64_t key = nk2d_frozen_key(c, sched, n);
     if (fc->key != key || fc->n != n) {
         // option "frozen_cache_after": that many years of a schedule run launch by launch before its cache is built.  Default
         // 0; -1: 0 for caches below 8 GB, 3 above.  Building a 100 GB cache takes 26 ms where a one-launch year saves 40

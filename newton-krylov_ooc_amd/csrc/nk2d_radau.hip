@@ -19,6 +19,7 @@
 // every decision (and the error estimate) and reproduces the smooth map
 // schedule -> y(T); see tests/test_gpu_comp_fcn.py.
 #include "nk2d_common.h"
+#include "nk2d_stream.h"
 
 #include <algorithm>
 #include <chrono>
@@ -53,6 +54,8 @@ struct Ctl {
     double pre_t, pre_h;
     double fingerprint;  // nk2d_fingerprint of the context at the start of the year (recorded with every step)
     bool no_persistent = false;   // the one-launch frozen year was tried and given up for this year
+    bool no_tape = false;         // ... and so was the year from a command tape (option "frozen_tape")
+    bool taped = false;           // this year ran from a tape
     int n_iter_prev = 0;          // Newton iterations of the last solve that converged (0: none yet)
 };
 
@@ -123,6 +126,11 @@ int solve_systems(Ctl& s, bool do_real, bool do_cplx, int* buf) {
 int predict(Ctl& s, double t, double h) {
     nk2d_ctx* c = s.c;
     if (!s.have_dense) {
+        if (c->tape_rec) {      // (recording a tape: zeroed before the tape runs -- nothing ahead of this on the tape reads them)
+            c->tape->zero_z = c->Z;
+            c->tape->zero_w = c->W;
+            return 0;
+        }
         NK2D_CHECK(c, hipMemsetAsync(c->Z, 0, sizeof(double) * 3 * c->nv, nk2d_s(c)));
         NK2D_CHECK(c, hipMemsetAsync(c->W, 0, sizeof(double) * 3 * c->nv, nk2d_s(c)));
         return 0;
@@ -149,6 +157,18 @@ int stage_planes(Ctl& s, double t, double h) {
     double times[3];
     for (int i = 0; i < 3; ++i) times[i] = t + (h * RC[i]);
     double* out[3] = {s.c->KV[0], s.c->KV[1], s.c->KV[2]};
+    if (s.c->tape_rec) {
+        // recording a tape: the planes of the first step have no command.  They run before the tape where nothing on it so far
+        // touches them (the first step's checkpoint copies only); anywhere else the launch refuses the tape (nk2d_s)
+        nk2d_tape* T = s.c->tape;
+        bool only_copies = !s.have_dense && T->first_out[0] == nullptr;
+        for (size_t k = 0; only_copies && k < T->cmds.size(); k += std::max(1u, T->cmds[k] >> 16))
+            only_copies = (T->cmds[k] & 0xffffu) == NK2D_OP_COPY;
+        if (only_copies) {
+            for (int i = 0; i < 3; ++i) { T->first_times[i] = times[i]; T->first_out[i] = out[i]; }
+            return 0;
+        }
+    }
     return nk2d_k_vmix(s.c, 3, times, out);
 }
 
@@ -426,6 +446,10 @@ int initial_step(Ctl& s, double* h_out) {
 int commit_step(Ctl& s, double t, double t_new, bool with_tend = false) {
     nk2d_ctx* c = s.c;
     if (with_tend) NK2D_TRY(nk2d_r_commit_tend(c, c->KV[3]));
+    else if (c->tape_rec) {    // recording a tape: the year's last commit is a launch behind it (a second one has no place)
+        if (c->tape->fin_out) c->tape_foreign++;
+        c->tape->fin_y = c->Y; c->tape->fin_z2 = c->Z + 2 * c->nv; c->tape->fin_out = c->YOLD;
+    }
     else NK2D_TRY(nk2d_r_axpy(c, c->Y, 1.0, c->Z + 2 * c->nv, c->YOLD));  // y_new into the spare buffer
     std::swap(c->Y, c->YOLD);                                          // Y = y_new, YOLD = y
     std::swap(c->Z, c->ZP);                                            // ZP = Z of this step
@@ -847,6 +871,182 @@ int replay_rows(Ctl& s, const double* sched, int64_t n, int64_t i0, bool check, 
     return 0;
 }
 
+// ---- a frozen year from a command tape (option "frozen_tape", nk2d_stream.h) ------------------------------------------
+// The commands of a frozen year are a function of the schedule and the context alone: nothing is decided and nothing is
+// read back before the year ends.  The first year of a schedule records them (replay_rows with the stream's commands going to
+// the tape), every year of that schedule -- the first included -- runs them as ONE launch of the resident kernel.
+nk2d_tape_ptrs tape_ptrs(const nk2d_ctx* c) {
+    nk2d_tape_ptrs p;
+    p.Y = c->Y; p.YOLD = c->YOLD; p.Z = c->Z; p.ZP = c->ZP; p.ZN = c->ZN; p.ZS = c->ZS;
+    for (int i = 0; i < 5; ++i) { p.KV[i] = c->KV[i]; p.JB[i] = c->JB[i]; }
+    for (int i = 0; i < 3; ++i) p.KVN[i] = c->KVN[i];
+    p.J[0] = c->JL; p.J[1] = c->JU; p.J[2] = c->JS; p.J[3] = c->JN; p.J[4] = c->JC;
+    return p;
+}
+void tape_set_ptrs(nk2d_ctx* c, const nk2d_tape_ptrs& p) {
+    c->Y = p.Y; c->YOLD = p.YOLD; c->Z = p.Z; c->ZP = p.ZP; c->ZN = p.ZN; c->ZS = p.ZS;
+    for (int i = 0; i < 5; ++i) { c->KV[i] = p.KV[i]; c->JB[i] = p.JB[i]; }
+    for (int i = 0; i < 3; ++i) c->KVN[i] = p.KVN[i];
+    c->JL = p.J[0]; c->JU = p.J[1]; c->JS = p.J[2]; c->JN = p.J[3]; c->JC = p.J[4];
+}
+// the same buffers, in whatever roles
+bool tape_same_buffers(const nk2d_tape_ptrs& a, const nk2d_tape_ptrs& b) {
+    std::vector<double*> x((double* const*)&a, (double* const*)(&a + 1)), y((double* const*)&b, (double* const*)(&b + 1));
+    std::sort(x.begin(), x.end());
+    std::sort(y.begin(), y.end());
+    return x == y;
+}
+void stats_add(nk2d_stats& a, const nk2d_stats& d) {
+    a.nfev += d.nfev; a.njev += d.njev; a.nlu += d.nlu; a.nsteps += d.nsteps; a.nrejected += d.nrejected;
+    a.nnewton += d.nnewton; a.nsolve += d.nsolve; a.nsweeps += d.nsweeps; a.nlaunch += d.nlaunch; a.nerr_checked += d.nerr_checked;
+}
+nk2d_stats stats_sub(const nk2d_stats& a, const nk2d_stats& b) {
+    nk2d_stats d = {};
+    d.nfev = a.nfev - b.nfev; d.njev = a.njev - b.njev; d.nlu = a.nlu - b.nlu; d.nsteps = a.nsteps - b.nsteps;
+    d.nrejected = a.nrejected - b.nrejected; d.nnewton = a.nnewton - b.nnewton; d.nsolve = a.nsolve - b.nsolve;
+    d.nsweeps = a.nsweeps - b.nsweeps; d.nlaunch = a.nlaunch - b.nlaunch; d.nerr_checked = a.nerr_checked - b.nerr_checked;
+    return d;
+}
+
+// every buffer of the context, besides the swapped ones, that a command may point at: a tape is run only while all of them are
+// where they were when it was recorded (nk2d_set_region reallocates PART, a longer schedule STEP_PART, a resume adds checkpoints)
+std::vector<const void*> tape_fixed_buffers(const nk2d_ctx* c) {
+    std::vector<const void*> b = {c->VV, c->KH, c->WT, c->WB, c->DZR, c->ZM0, c->ZM1, c->DM, c->DMR, c->DYR, c->BLDMAX, c->MASK,
+                                  c->WN, c->LIGHT, c->UPR, c->YLIN, c->SMSREC, c->RESTREC, c->F, c->W, c->BR, c->BCR, c->BCI,
+                                  c->XR[0], c->XR[1], c->XCR[0], c->XCR[1], c->XCI[0], c->XCI[1], c->TMP, c->TMP2,
+                                  c->FR_INV, c->FC_INVR, c->FC_INVI, c->FR_TAB, c->FC_TABR, c->FC_TABI, c->FR32_INV, c->FC32_INVR,
+                                  c->FC32_INVI, c->FR32_TAB, c->FC32_TABR, c->FC32_TABI, c->PART, c->PART2, c->STEP_PART,
+                                  c->STEP_NORM, c->RED};
+    b.insert(b.end(), c->ckpt.begin(), c->ckpt.end());
+    return b;
+}
+
+// whether this context's frozen years may run from tapes (not with history samples: they have no command; not sharded: the
+// controller's norms go through the hook; not factor_fp32: the resident kernel has double precision tables only)
+bool tape_eligible(const Ctl& s) {
+    const nk2d_ctx* c = s.c;
+    return c->frozen_tape && !s.no_tape && c->hist_n == 0 && !c->norm_hook && !c->norm_hook_vec && !c->factor_fp32;
+}
+
+// The frozen year of rows 0 .. n-1 from the tape of this schedule, recorded first where there is none.  0: the year ran (the
+// controller, the buffers' roles and the counters are where the recorded controller left them); 1: not taped, nothing has
+// run; 3: the year must be rerun by the existing path from x (a kernel that gave up, or a recording that met a launch with
+// no command -- which ran on the spot).
+int tape_year(Ctl& s, const double* sched, int64_t n, std::vector<char>& err_done) {
+    nk2d_ctx* c = s.c;
+    const uint64_t key = nk2d_frozen_key(c, sched, n);
+    if (!c->tape) c->tape = new nk2d_tape();
+    nk2d_tape* T = c->tape;
+    if (T->refused == key) { c->tape_fallbacks++; return 1; }
+    NK2D_TRY(nk2d_stream_ready(c));
+    const nk2d_tape_ptrs now = tape_ptrs(c);
+    // (the checkpoints a resume adds behind the recorded ones are not on the tape: a prefix that matches is enough)
+    const std::vector<const void*> fixed = tape_fixed_buffers(c);
+    const bool have = T->key == key && T->rows == n && fixed.size() >= T->fixed.size() &&
+                      std::equal(T->fixed.begin(), T->fixed.end(), fixed.begin()) && tape_same_buffers(T->p0, now);
+    if (!have) {
+        T->key = 0;
+        T->cmds.clear();
+        T->ncmd = 0;
+        T->zero_z = T->zero_w = nullptr;
+        for (int i = 0; i < 3; ++i) T->first_out[i] = nullptr;
+        T->fin_y = T->fin_z2 = nullptr;
+        T->fin_out = nullptr;
+        const Ctl s0 = s;
+        const nk2d_stats st0 = c->st;
+        const int64_t sweep0 = c->sweep_launches;
+        const double bytes0 = c->fused_bytes_all;
+        int64_t shape0[4];
+        double shape_bytes0[4];
+        for (int k = 0; k < 4; ++k) { shape0[k] = c->shape_cnt[k]; shape_bytes0[k] = c->shape_bytes[k]; }
+        const int stream_on0 = c->stream_on;
+        c->stream_on = 1;
+        c->tape_rec = 1;
+        c->tape_foreign = 0;
+        ReplayLocal L;
+        L.err_done = &err_done;
+        const int rc = replay_rows(s, sched, n, 0, true, L);
+        c->tape_rec = 0;
+        c->stream_on = stream_on0;
+        c->part_cur = nullptr;
+        if (rc != 0) return rc;
+        if (c->tape_foreign != 0 || !T->fin_out) {
+            c->tape_fallbacks++;
+            T->refused = key;
+            T->cmds.clear();
+            T->ncmd = 0;
+            return 3;
+        }
+        // what the recorded controller left behind
+        T->p0 = now;
+        T->p1 = tape_ptrs(c);
+        T->fixed = tape_fixed_buffers(c);
+        T->st = stats_sub(c->st, st0);
+        T->sweep_launches = c->sweep_launches - sweep0;
+        T->fused_bytes = c->fused_bytes_all - bytes0;
+        for (int k = 0; k < 4; ++k) { T->shape_cnt[k] = c->shape_cnt[k] - shape0[k]; T->shape_bytes[k] = c->shape_bytes[k] - shape_bytes0[k]; }
+        T->lu[0] = c->lu_cre; T->lu[1] = c->lu_ccr; T->lu[2] = c->lu_cci;
+        T->factor_pending = c->factor_pending;
+        T->err_done = err_done;
+        const double ctl[8] = {s.t, s.t_jac, s.h_lu, s.dense_t_old, s.dense_h, s.pre_t, s.pre_h, 0.0};
+        const int ctl_i[6] = {s.m_real, s.m_cplx, s.have_lu, s.have_dense, s.pre_setup, 0};
+        std::copy(ctl, ctl + 8, T->ctl);
+        std::copy(ctl_i, ctl_i + 6, T->ctl_i);
+        NK2D_TRY(nk2d_tape_upload(c, T));
+        T->key = key;
+        T->rows = n;
+        c->tape_builds++;
+        // back to where the year starts: the tape books all of it when it runs
+        s = s0;
+        c->st = st0;
+        c->sweep_launches = sweep0;
+        c->fused_bytes_all = bytes0;
+        for (int k = 0; k < 4; ++k) { c->shape_cnt[k] = shape0[k]; c->shape_bytes[k] = shape_bytes0[k]; }
+        tape_set_ptrs(c, now);
+    } else if (std::memcmp(&T->p0, &now, sizeof(now)) != 0) {
+        // the buffers in other roles than when the tape was recorded: the year's start (the state, the mixing plane at t0
+        // and the Jacobian planes start_year has just computed) into the buffers the tape reads it from
+        const size_t np = c->np, nv = c->nv;
+        auto move = [&](double* to, const double* from, size_t count) -> int {
+            if (to != from) NK2D_CHECK(c, hipMemcpyAsync(to, from, sizeof(double) * count, hipMemcpyDeviceToDevice, nk2d_s(c)));
+            return 0;
+        };
+        NK2D_TRY(move(T->p0.Y, now.Y, nv));
+        NK2D_TRY(move(T->p0.KV[3], now.KV[3], c->kv_len));
+        for (int k = 0; k < 5; ++k) NK2D_TRY(move(T->p0.J[k], now.J[k], np));
+        tape_set_ptrs(c, T->p0);
+    }
+    if (T->zero_z) {
+        NK2D_CHECK(c, hipMemsetAsync(T->zero_z, 0, sizeof(double) * 3 * c->nv, nk2d_s(c)));
+        NK2D_CHECK(c, hipMemsetAsync(T->zero_w, 0, sizeof(double) * 3 * c->nv, nk2d_s(c)));
+    }
+    if (T->first_out[0]) NK2D_TRY(nk2d_k_vmix(c, 3, T->first_times, T->first_out));
+    const int trc = nk2d_tape_run(c, T);
+    if (trc == 1) { c->tape_fallbacks++; tape_set_ptrs(c, now); return 1; }
+    if (trc == NK2D_RC_STREAM_LOST) {
+        c->tape_timeouts++;
+        c->st.nbarrier_timeouts++;
+        return 3;
+    }
+    if (trc != 0) return trc;
+    NK2D_TRY(nk2d_r_axpy(c, T->fin_y, 1.0, T->fin_z2, T->fin_out));
+    tape_set_ptrs(c, T->p1);
+    stats_add(c->st, T->st);
+    c->sweep_launches += T->sweep_launches;
+    c->fused_bytes_all += T->fused_bytes;
+    for (int k = 0; k < 4; ++k) { c->shape_cnt[k] += T->shape_cnt[k]; c->shape_bytes[k] += T->shape_bytes[k]; }
+    c->lu_cre = T->lu[0]; c->lu_ccr = T->lu[1]; c->lu_cci = T->lu[2];
+    c->factor_pending = T->factor_pending;
+    err_done = T->err_done;
+    s.t = T->ctl[0]; s.t_jac = T->ctl[1]; s.h_lu = T->ctl[2]; s.dense_t_old = T->ctl[3]; s.dense_h = T->ctl[4];
+    s.pre_t = T->ctl[5]; s.pre_h = T->ctl[6];
+    s.m_real = T->ctl_i[0]; s.m_cplx = T->ctl_i[1]; s.have_lu = T->ctl_i[2] != 0; s.have_dense = T->ctl_i[3] != 0;
+    s.pre_setup = T->ctl_i[4] != 0;
+    s.taped = true;
+    c->tape_years_run++;
+    return 0;
+}
+
 int run_replay(Ctl& s, const double* sched, int64_t n, bool check) {
     nk2d_ctx* c = s.c;
     if (!check) {
@@ -990,8 +1190,15 @@ int run_replay(Ctl& s, const double* sched, int64_t n, bool check) {
             L.kv3_at_t = false;
             L.f_at_t = false;
         }
-        NK2D_TRY(replay_rows(s, cur, n, start, true, L));
-        if (c->stream_on) {
+        // the first pass from a command tape (option "frozen_tape"), where the one-launch year above did not take the year
+        int trc = 1;
+        if (round == 0 && tape_eligible(s)) {
+            trc = tape_year(s, cur, n, err_done);
+            if (trc == 3) return 3;
+            if (trc != 0 && trc != 1) return trc;
+        }
+        if (trc != 0) NK2D_TRY(replay_rows(s, cur, n, start, true, L));
+        if (trc != 0 && c->stream_on) {
             // the year ran as a command stream: the kernel ends here; had it given up on the way, the year is handed back
             // (return 3: the caller restarts it from x, launch by launch)
             const int erc = nk2d_stream_end(c);
@@ -1141,13 +1348,15 @@ int nk2d_radau_year(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, nk2d_stats* stats, con
                 c->fused_bytes_all = bytes0;
                 c->sweep_launches = launches0;
                 s.no_persistent = true;
+                s.no_tape = true;
+                s.taped = false;
                 s.t = c->d.t0;
                 s.have_lu = false; s.have_dense = false; s.pre_setup = false;
                 NK2D_TRY(start_year());
                 rrc = run_replay(s, replay, replay_n, replay_own);
             }
             if (rrc != 0) return rrc;
-            if (was_stream && c->stream_on) { c->stream_years_run++; c->stream_lost = 0; }
+            if (was_stream && c->stream_on && !s.taped) { c->stream_years_run++; c->stream_lost = 0; }
         }
         else {
             // The free-running year as a command stream (nk2d_stream.h): the launches of run_free become commands of ONE

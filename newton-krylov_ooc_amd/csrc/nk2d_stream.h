@@ -17,6 +17,8 @@
 
 #include "nk2d_bodies.h"
 
+#include <vector>
+
 enum { NK2D_OP_EXIT = 1, NK2D_OP_SETUP = 2, NK2D_OP_NEWTON = 3, NK2D_OP_ERR = 4, NK2D_OP_BOUNDARY = 5,
        // the several-sweep error estimate and the second estimate of a rejected step, launch for launch
        NK2D_OP_SWEEP = 6, NK2D_OP_ERR_RHS = 7, NK2D_OP_ERR_RHS2 = 8, NK2D_OP_ERR_NORM = 9, NK2D_OP_COPY = 10,
@@ -92,9 +94,48 @@ struct StreamArgs {
                                         // memory), bit 1: so does W of its columns
     double* W;                          // the context's W (3 nv): loaded into LDS when the kernel starts, stored back when it ends
     unsigned long long* prof;           // [nwg][12]: ticks waiting for a command, executing, waiting for neighbours; commands; per op
+    const unsigned* tape;               // the tape flavour (k_stream<..., true>): the year's commands in HBM, packed, EXIT last
+    size_t tape_dwords;
+};
+
+// A frozen year recorded as commands (option "frozen_tape"): what nk2d_stream_push would have written to the ring, packed by
+// cmd_dwords (dword 0: op | dwords << 16), in HBM, read by the resident kernel itself -- no host in the loop.  Besides the
+// commands it keeps what the controller left behind on the host, so that a year run from the tape ends where the recorded
+// controller ended: the roles of the context's buffers before and after, the step's last commit (a launch behind the tape),
+// the counters the year books, the rows whose error estimate was evaluated.
+struct nk2d_tape_ptrs {
+    double *Y, *YOLD, *Z, *ZP, *ZN, *ZS, *KV[5], *KVN[3], *J[5], *JB[5];
+};
+struct nk2d_tape {
+    uint64_t key = 0;                   // schedule key ^ nk2d_fingerprint ^ frozen_err_check (nk2d_frozen_key); 0: none
+    uint64_t refused = 0;               // a schedule whose year cannot be taped (a launch with no command inside it)
+    int64_t rows = 0;
+    std::vector<unsigned> cmds;         // host copy, packed
+    int64_t ncmd = 0;                   // commands, EXIT included
+    unsigned* dev = nullptr;
+    size_t dev_dwords = 0;              // allocated
+    nk2d_tape_ptrs p0 = {}, p1 = {};    // buffer roles when the tape starts / after the year
+    std::vector<const void*> fixed;     // every other buffer of the context a command may point at, when it was recorded
+    double* zero_z = nullptr;           // Z and W zeroed before the first step (the first step has no dense output)
+    double* zero_w = nullptr;
+    double first_times[3] = {0, 0, 0};  // ... and the mixing planes of its stage times, a launch before the tape (no command)
+    double* first_out[3] = {nullptr, nullptr, nullptr};
+    const double *fin_y = nullptr, *fin_z2 = nullptr;   // the last step's commit: fin_out <- fin_y + fin_z2, a launch
+    double* fin_out = nullptr;
+    nk2d_stats st = {};                 // what the recorded year booked
+    int64_t sweep_launches = 0, shape_cnt[4] = {0, 0, 0, 0};
+    double fused_bytes = 0.0, shape_bytes[4] = {0, 0, 0, 0};
+    double lu[3] = {0, 0, 0};
+    int factor_pending = 0;
+    std::vector<char> err_done;
+    double ctl[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the controller's state after the year (nk2d_radau.hip)
+    int ctl_i[6] = {0, 0, 0, 0, 0, 0};
 };
 
 // host side (nk2d_stream.hip; what the integrator itself calls is declared in nk2d_common.h)
 int nk2d_stream_push(nk2d_ctx* c, StreamCmd& cmd, bool notify, unsigned* seq_out = nullptr);
 int nk2d_stream_wait(nk2d_ctx* c, unsigned seq);
 unsigned nk2d_stream_last_seq(const nk2d_ctx* c);
+// the tape: upload after recording, run (0; NK2D_RC_STREAM_LOST when the kernel gave up, 1 when it cannot be resident)
+int nk2d_tape_upload(nk2d_ctx* c, nk2d_tape* T);
+int nk2d_tape_run(nk2d_ctx* c, nk2d_tape* T);

@@ -63,18 +63,23 @@ __device__ __forceinline__ void stream_relay(const StreamArgs& A, int lane) {
     }
 }
 
-template <int E, int KIND>
+// TAPE (option "frozen_tape"): the commands come from a tape in HBM instead of the ring -- no relay, no stamps, no ring to
+// poll, nothing to tell the host.  Wave 0 loads command k+1 into registers when command k starts and puts it into the second
+// of two LDS buffers when its part of command k is done; between two commands a workgroup waits for its lateral neighbours
+// only.  Everything else -- the device functions, the hand-over, the bounded waits -- is the host-fed kernel's.
+template <int E, int KIND, bool TAPE>
 __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) {
     __shared__ int lds_ok;
-    __shared__ StreamCmd cmd;
+    __shared__ StreamCmd cmdb[TAPE ? 2 : 1];
+    int cur = 0;
     const int lane = threadIdx.x & 63;
     const int tw = uni_i((int)(threadIdx.x >> 6));          // the wave's place in its workgroup = its tracer
-    if (blockIdx.x == 0) {
+    if (!TAPE && blockIdx.x == 0) {
         // (no relay where the host writes its commands straight into the ring in HBM)
         if (tw == 0 && A.h_ring != nullptr) stream_relay(A, lane);
         return;
     }
-    const int wg = (int)blockIdx.x - 1;
+    const int wg = TAPE ? (int)blockIdx.x : (int)blockIdx.x - 1;
     const int nw = (int)(blockDim.x >> 6);
     const int j0 = wg * A.cpw, j1 = min(j0 + A.cpw, P.ny);   // this workgroup's ypos columns, every tracer of them
     const int left = (wg > 0) ? wg - 1 : -1, right = (wg < A.nwg - 1) ? wg + 1 : -1;
@@ -116,6 +121,7 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
     // its stamp) -- which it then copies into LDS for the workgroup.  Before the first command there is nobody to wait for.
     // Returns (to wave 0's lanes) 1, or 0 when a wait ran over the time limit or another workgroup has given up.
     auto wait_and_fetch = [&](unsigned done_seq, bool with_neighbours, long long& ticks_nb, long long& ticks_cmd) -> int {
+        StreamCmd& cmd = cmdb[0];
         const unsigned next = done_seq + 1u;
         const size_t slot = (size_t)(next % NK2D_RING_SLOTS) * NK2D_CMD_DWORDS;
         const int other = with_neighbours ? ((lane == 0) ? left : ((lane == 1) ? right : -1)) : -1;
@@ -124,14 +130,17 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
         const long long t_begin = (long long)__builtin_amdgcn_s_memrealtime();
         long long t_nb_ok = t_begin;
         for (;;) {
-            const unsigned long long a = ld_pair_dev(A.d_ring + slot + lane);
-            const unsigned long long b = ld_pair_dev(A.d_ring + slot + 64 + lane);
-            const unsigned long long d = ld_pair_dev(A.d_ring + slot + 128 + lane);
             if (!nb_ok) {
                 unsigned v = done_seq;
                 if (other >= 0) v = __hip_atomic_load(A.flags + (size_t)other * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (__all((int)((int)(v - done_seq) >= 0))) { nb_ok = true; t_nb_ok = (long long)__builtin_amdgcn_s_memrealtime(); }
             }
+            if constexpr (TAPE) {      // (the next command is in LDS already)
+                if (nb_ok) { ticks_nb += t_nb_ok - t_begin; return 1; }
+            } else {
+            const unsigned long long a = ld_pair_dev(A.d_ring + slot + lane);
+            const unsigned long long b = ld_pair_dev(A.d_ring + slot + 64 + lane);
+            const unsigned long long d = ld_pair_dev(A.d_ring + slot + 128 + lane);
             const unsigned head = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)a, 0);
             const int ndw = ((unsigned)__builtin_amdgcn_readlane((int)(unsigned)(a >> 32), 0) == next) ? (int)(head >> 16) : NK2D_CMD_DWORDS;
             if (nb_ok && __all((int)(((unsigned)(a >> 32) == next || lane >= ndw) && ((unsigned)(b >> 32) == next || 64 + lane >= ndw) &&
@@ -145,6 +154,7 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
                 ticks_cmd += t_end - t_nb_ok;
                 return 1;
             }
+            }
             const int ab = __builtin_amdgcn_readfirstlane(
                 (lane == 0) ? __hip_atomic_load(A.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0);
             const bool late = ((++spins & 63) == 0 || A.spin_ticks == 0) &&
@@ -156,7 +166,30 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
             __builtin_amdgcn_s_sleep(1);
         }
     };
-    if (tw == 0) {
+    // the tape: wave 0's loads of the command at dword `at` (three dwords a lane), and their way into an LDS buffer
+    size_t tape_next = 0;
+    auto tape_load = [&](size_t at, unsigned& a, unsigned& b, unsigned& d) {
+        a = (at + lane < A.tape_dwords) ? A.tape[at + lane] : 0u;
+        b = (at + 64 + lane < A.tape_dwords) ? A.tape[at + 64 + lane] : 0u;
+        d = (at + 128 + lane < A.tape_dwords) ? A.tape[at + 128 + lane] : 0u;
+    };
+    auto tape_put = [&](StreamCmd& dst, unsigned a, unsigned b, unsigned d) {
+        const unsigned head = (unsigned)__builtin_amdgcn_readlane((int)a, 0);
+        const int ndw = min((int)(head >> 16), NK2D_CMD_DWORDS);
+        unsigned* dw = reinterpret_cast<unsigned*>(&dst);
+        if (lane < ndw) dw[lane] = (lane == 0) ? (head & 0xffffu) : a;
+        if (64 + lane < ndw) dw[64 + lane] = b;
+        if (128 + lane < ndw) dw[128 + lane] = d;
+        tape_next += (size_t)max(ndw, 1);
+    };
+    if (TAPE) {
+        if (tw == 0) {
+            unsigned a, b, d;
+            tape_load(0, a, b, d);
+            tape_put(cmdb[0], a, b, d);
+            if (lane == 0) lds_ok = 1;
+        }
+    } else if (tw == 0) {
         const int good = wait_and_fetch(seq - 1u, false, t_nb, t_cmd);
         if (lane == 0) lds_ok = good;
     }
@@ -164,12 +197,15 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
     if (lds_ok == 0) status = 1;
     while (status == 0) {
         const long long t1 = (long long)__builtin_amdgcn_s_memrealtime();
+        StreamCmd& cmd = cmdb[cur];
         const int op = uni_i(cmd.op), flags = uni_i(cmd.flags);
         if (op == NK2D_OP_EXIT) {
             if (threadIdx.x == 0)
                 __hip_atomic_store(A.flags + (size_t)wg * 32, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
         }
+        unsigned ta = 0, tb = 0, td = 0;     // (the tape: the next command, on its way while this one executes)
+        if (TAPE && tw == 0) tape_load(tape_next, ta, tb, td);
         // ---- its work on this workgroup's columns: wave tw takes tracer tw (a one-wave workgroup every tracer in turn)
         if (op == NK2D_OP_NEWTON) {
             for (int tr = tw; tr < P.tc; tr += nw)
@@ -297,13 +333,14 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
         // completed (and, where the host waits for it, stamps pinned memory), waits for its two lateral neighbours and
         // for the next command
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (TAPE && tw == 0) tape_put(cmdb[cur ^ 1], ta, tb, td);
         if (A.fences) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
         const long long t2 = (long long)__builtin_amdgcn_s_memrealtime();
         if (tw == 0) {
             if (lane == 0) {
                 __hip_atomic_store(A.flags + (size_t)wg * 32, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (flags & NK2D_CMD_NOTIFY) __hip_atomic_store(A.h_done + wg, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (!TAPE && (flags & NK2D_CMD_NOTIFY)) __hip_atomic_store(A.h_done + wg, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             const int good = wait_and_fetch(seq, true, t_nb, t_cmd);
             if (lane == 0) lds_ok = good;
@@ -317,6 +354,7 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
             if (bucket >= 0) { t_op[bucket] += t2 - t1; ++n_op[bucket]; }
         }
         ++seq;
+        if (TAPE) cur ^= 1;
     }
     if (w_in_lds) {      // W back to memory: whatever runs behind this kernel (launches, the next kernel of the year) finds it there
         for (int tr = tw; tr < P.tc; tr += nw)
@@ -343,17 +381,17 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
     if (wg == 0 && threadIdx.x == 0) A.out[1] = (double)seq;
 }
 
-template <int E, int KIND>
+template <int E, int KIND, bool TAPE>
 __global__ void __launch_bounds__(NK2D_BLOCK) k_stream(DevP P, StreamArgs A) {
-    stream_body<E, KIND>(P, A);
+    stream_body<E, KIND, TAPE>(P, A);
 }
 // The same within 256 registers, so that a SIMD holds TWO waves (option "stream_two_waves"; phosphorus from five levels per
 // lane, where a wave of k_stream holds 280 - 390 registers and the chip therefore 1 024 waves: the 1 248 (tracer, ypos)
 // columns of phosphorus at 416 x 416 are then two rounds per command on half as many workgroups).  What does not fit the
 // registers lives in scratch memory.
-template <int E, int KIND>
+template <int E, int KIND, bool TAPE>
 __global__ void __launch_bounds__(NK2D_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) k_stream_w2(DevP P, StreamArgs A) {
-    stream_body<E, KIND>(P, A);
+    stream_body<E, KIND, TAPE>(P, A);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -435,26 +473,30 @@ int nk2d_stream_eligible(const nk2d_ctx* c) {
 template <int E, int KIND>
 constexpr bool kStreamHasTwoWaves = KIND == 1 && E >= 5;
 
-template <int E, int KIND>
+template <int E, int KIND, bool TAPE>
 static hipError_t stream_launch_one(nk2d_ctx* c, dim3 grid, dim3 block, DevP& P, StreamArgs& A, int* max_blocks, size_t lds_bytes,
                                     bool two_waves) {
     if constexpr (kStreamHasTwoWaves<E, KIND>) {
         if (two_waves) {
-            if (max_blocks) return hipOccupancyMaxActiveBlocksPerMultiprocessor(max_blocks, k_stream_w2<E, KIND>, (int)block.x, lds_bytes);
-            hipLaunchKernelGGL((k_stream_w2<E, KIND>), grid, block, lds_bytes, c->stream_, P, A);
+            if (max_blocks) return hipOccupancyMaxActiveBlocksPerMultiprocessor(max_blocks, k_stream_w2<E, KIND, TAPE>, (int)block.x, lds_bytes);
+            hipLaunchKernelGGL((k_stream_w2<E, KIND, TAPE>), grid, block, lds_bytes, c->stream_, P, A);
             return hipGetLastError();
         }
     } else if (two_waves) {
         return hipErrorInvalidValue;
     }
-    if (max_blocks) return hipOccupancyMaxActiveBlocksPerMultiprocessor(max_blocks, k_stream<E, KIND>, (int)block.x, lds_bytes);
-    hipLaunchKernelGGL((k_stream<E, KIND>), grid, block, lds_bytes, c->stream_, P, A);
+    if (max_blocks) return hipOccupancyMaxActiveBlocksPerMultiprocessor(max_blocks, k_stream<E, KIND, TAPE>, (int)block.x, lds_bytes);
+    hipLaunchKernelGGL((k_stream<E, KIND, TAPE>), grid, block, lds_bytes, c->stream_, P, A);
     return hipGetLastError();
 }
 static hipError_t stream_launch(nk2d_ctx* c, dim3 grid, dim3 block, DevP& P, StreamArgs& A, int* max_blocks, size_t lds_bytes,
-                                bool two_waves) {
+                                bool two_waves, bool tape = false) {
     hipError_t rc = hipErrorInvalidValue;
-    NK2D_DISPATCH_EK(c->E, c->kind, rc = (stream_launch_one<EE, KK>(c, grid, block, P, A, max_blocks, lds_bytes, two_waves)));
+    if (tape) {
+        NK2D_DISPATCH_EK(c->E, c->kind, rc = (stream_launch_one<EE, KK, true>(c, grid, block, P, A, max_blocks, lds_bytes, two_waves)));
+    } else {
+        NK2D_DISPATCH_EK(c->E, c->kind, rc = (stream_launch_one<EE, KK, false>(c, grid, block, P, A, max_blocks, lds_bytes, two_waves)));
+    }
     return rc;
 }
 // dynamic shared memory of a launch whose workgroups own cpw ypos columns each
@@ -531,6 +573,12 @@ static int stream_alloc(nk2d_ctx* c) {
 int nk2d_stream_ready(nk2d_ctx* c) { return stream_alloc(c); }
 
 void nk2d_stream_free(nk2d_ctx* c) {
+    if (c->tape) {
+        (void)hipStreamSynchronize(c->stream_);
+        if (c->tape->dev) (void)hipFree(c->tape->dev);
+        delete c->tape;
+        c->tape = nullptr;
+    }
     nk2d_stream_state* S = c->strm;
     if (!S) return;
     if (S->running) (void)nk2d_stream_pause(c);
@@ -711,6 +759,21 @@ int nk2d_stream_wait_part(nk2d_ctx* c, const double* name, int n) {
 }
 
 int nk2d_stream_push(nk2d_ctx* c, StreamCmd& cmd, bool notify, unsigned* seq_out) {
+    if (c->tape_rec) {
+        // recording a tape (option "frozen_tape"): the command goes to the tape, packed; nothing runs, nothing is counted.
+        // A command behind the year's last commit (a launch, after the tape) would run out of order: the tape is refused.
+        nk2d_tape* T = c->tape;
+        if (T->fin_out) c->tape_foreign++;
+        unsigned dw[NK2D_CMD_DWORDS] = {0};
+        cmd.flags &= ~NK2D_CMD_NOTIFY;
+        std::memcpy(dw, &cmd, sizeof(StreamCmd));
+        const int ndw = cmd_dwords(cmd.op);
+        dw[0] = (unsigned)cmd.op | ((unsigned)ndw << 16);
+        T->cmds.insert(T->cmds.end(), dw, dw + ndw);
+        T->ncmd++;
+        if (seq_out) *seq_out = 0;
+        return 0;
+    }
     NK2D_TRY(stream_alloc(c));
     nk2d_stream_state* S = c->strm;
     if (S->lost) return NK2D_RC_STREAM_LOST;
@@ -779,5 +842,91 @@ int nk2d_stream_profile(nk2d_ctx* c, double* out12) {
     for (int wg = 0; wg < S->nwg; ++wg)
         for (int i = 0; i < 12; ++i) out12[i] += (double)h[(size_t)12 * wg + i];
     for (int i = 0; i < 12; ++i) out12[i] *= ((i < 3 || (i >= 4 && i < 8)) ? 0.01 : 1.0) / S->nwg;      // ticks of 10 ns -> us
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the tape (option "frozen_tape", nk2d_stream.h)
+// ---------------------------------------------------------------------------------------------------------------------
+// the recorded commands, EXIT appended, into HBM (once per schedule; the allocation is kept and grows)
+int nk2d_tape_upload(nk2d_ctx* c, nk2d_tape* T) {
+    const unsigned exit_dw = (unsigned)NK2D_OP_EXIT | ((unsigned)cmd_dwords(NK2D_OP_EXIT) << 16);
+    T->cmds.push_back(exit_dw);
+    for (int k = 1; k < cmd_dwords(NK2D_OP_EXIT); ++k) T->cmds.push_back(0u);
+    T->ncmd++;
+    const size_t need = T->cmds.size();
+    if (T->dev_dwords < need) {
+        NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+        if (T->dev) NK2D_CHECK(c, hipFree(T->dev));
+        T->dev = nullptr;
+        T->dev_dwords = 0;
+        NK2D_CHECK(c, hipMalloc((void**)&T->dev, sizeof(unsigned) * need));
+        T->dev_dwords = need;
+    }
+    NK2D_CHECK(c, hipMemcpyAsync(T->dev, T->cmds.data(), sizeof(unsigned) * need, hipMemcpyHostToDevice, nk2d_s(c)));
+    return 0;
+}
+
+void nk2d_tape_forget(nk2d_ctx* c) {
+    if (c->tape) c->tape->key = 0;
+}
+
+int64_t nk2d_tape_size(const nk2d_ctx* c, int what) {
+    const nk2d_tape* T = c->tape;
+    if (!T || !T->key) return 0;
+    return what == 0 ? (int64_t)(sizeof(unsigned) * T->cmds.size()) : T->ncmd;
+}
+
+// The whole frozen year as ONE launch of the tape flavour of the resident kernel, on the shape of the context's command
+// stream (its workgroups, columns per workgroup, LDS copies, one or two waves to a SIMD).  The host waits for the end of the
+// kernel only: NK2D_RC_STREAM_LOST when a workgroup gave up on a wait (the caller reruns the year by the existing path),
+// 1 when the tape flavour cannot have every workgroup resident (nothing has run).
+int nk2d_tape_run(nk2d_ctx* c, nk2d_tape* T) {
+    NK2D_TRY(stream_alloc(c));
+    nk2d_stream_state* S = c->strm;
+    (void)nk2d_s(c);      // (a host-fed kernel still running ends first)
+    DevP P = make_devp(c);
+    StreamArgs A = {};
+    const size_t lds = stream_lds_bytes(c, S->cpw, S->coef_lds);
+    {
+        hipDeviceProp_t prop;
+        NK2D_CHECK(c, hipGetDeviceProperties(&prop, c->dev));
+        int per_cu = 0;
+        NK2D_CHECK(c, stream_launch(c, dim3(1), dim3(64 * S->nw), P, A, &per_cu, lds, S->two_waves, true));
+        if (per_cu * prop.multiProcessorCount < S->nwg) return 1;
+    }
+    A.abort_flag = (int*)S->d_sync;
+    A.flags = (unsigned*)(S->d_sync + 4096);
+    A.h_status = S->h_status; A.out = S->d_out;
+    A.seq0 = S->seq + 1;
+    A.nwg = S->nwg; A.cpw = S->cpw;
+    A.spin_ticks = (long long)(c->barrier_timeout_ms * 1.0e5);
+    A.fences = c->year_fences;
+    A.prof = S->d_prof;
+    A.coef_lds = S->coef_lds ? 3 : 0;
+    A.W = c->W;
+    A.tape = T->dev;
+    A.tape_dwords = T->cmds.size();
+    const int waves = S->nwg * S->nw;
+    nk2d_turn_take(waves);
+    const hipError_t rc = stream_launch(c, dim3(S->nwg), dim3(64 * S->nw), P, A, nullptr, lds, S->two_waves, true);
+    if (rc != hipSuccess) {
+        nk2d_turn_give(waves);
+        NK2D_CHECK(c, rc);
+    }
+    // (the stamps of the workgroups' flags go on from here: a host-fed kernel after this one starts behind the EXIT)
+    S->seq += (unsigned)T->ncmd;
+    S->done_upto = S->seq;
+    const hipError_t c1 = hipMemcpyAsync(S->h_out, S->d_out, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream_);
+    const hipError_t c2 = (c1 == hipSuccess) ? hipStreamSynchronize(c->stream_) : c1;
+    nk2d_turn_give(waves);
+    NK2D_CHECK(c, c2);
+    c->st.nlaunch++;
+    if (S->h_out[0] != 0.0 || __atomic_load_n(S->h_status, __ATOMIC_RELAXED) != 0) {
+        std::memset(S->h_status, 0, sizeof(unsigned) * 16);
+        NK2D_CHECK(c, hipMemset(S->d_sync, 0, 4096));
+        NK2D_CHECK(c, hipMemset(S->d_out, 0, sizeof(double) * 8));
+        return NK2D_RC_STREAM_LOST;
+    }
     return 0;
 }

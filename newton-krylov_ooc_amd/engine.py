@@ -205,6 +205,8 @@ class ModuleEngine:
         self._precond_ready = False
         if "NK2D_STREAM_YEARS" in os.environ:
             self.set_option("stream_years", float(os.environ["NK2D_STREAM_YEARS"]))
+        if "NK2D_FROZEN_TAPE" in os.environ:
+            self.set_option("frozen_tape", float(os.environ["NK2D_FROZEN_TAPE"]))
         self.set_option("jac_fresh", float(os.environ.get("NK2D_JAC_FRESH", DEFAULT_JAC_FRESH)))
         self.set_option("growth_cap", float(os.environ.get("NK2D_GROWTH_CAP", DEFAULT_GROWTH_CAP)))
         self.set_option("jac_stage", float(os.environ.get("NK2D_JAC_STAGE", DEFAULT_JAC_STAGE)))
