@@ -3,7 +3,12 @@
 
 Run ONLY in the build container (needs /root/reference):
 
-    python tests/golden/gen_golden.py
+    python tests/golden/gen_golden.py                 # every small fixture
+    python tests/golden/gen_golden.py forced_file     # only the file-driven forced fixtures
+    python tests/golden/gen_golden.py deep_modules    # phosphorus_416x4.npz and forced_file_sink_thres_416x4.npz: seven
+                                                      # levels per lane, a solve_ivp year each (about 4 min and 1 min on
+                                                      # one BLAS thread); `deep_modules phosphorus` / `deep_modules forced`
+                                                      # write one of the two
 
 It imports `nk_ooc.py_driver_2d.{advection,horiz_mix,vert_mix,iage}`,
 `nk_ooc.spatial_axis` and `nk_ooc.krylov_solver` from /root/reference.  Three
@@ -304,8 +309,8 @@ def gen_forced_file(tag, nz, ny, restore_opt, sms_opt, sink_thres, seed, with_fc
     print("wrote forced", tag)
 
 
-def gen_phosphorus(tag, nz, ny, seed, with_fcn=False):
-    """reference phosphorus module: tendencies, Jacobian, one forward year"""
+def gen_phosphorus(tag, nz, ny, seed, with_fcn=False, times=(0.0, 0.3, 0.66)):
+    """reference phosphorus module: tendencies and Jacobian at `times` (fractions of the year), one forward year"""
     from scipy import integrate
 
     from nk_ooc.py_driver_2d.advection import Advection
@@ -329,7 +334,7 @@ def gen_phosphorus(tag, nz, ny, seed, with_fcn=False):
     tm.params = phosphorus.gen_params({})
     tm.pop_sink_work = np.zeros((nz + 1, ny))
     year = 365.0 * 86400.0
-    times = [0.0, 0.3 * year, 0.66 * year]
+    times = [frac * year for frac in times]
     rng = np.random.default_rng(seed)
     # positive, vertically structured state (the init_iterate profiles of tracer_module_defs.yaml)
     prof = [np.interp(depth.mid, zs, vs) for zs, vs in (([1.3e2, 2.6e2], [5.5e-3, 4.1e0]),
@@ -370,6 +375,18 @@ def gen_lstsq(seed):
         out[f"coeff{case}"] = _comp_krylov_basis_coeffs(beta, h)
     np.savez_compressed(os.path.join(HERE, "lstsq.npz"), **out)
     print("wrote lstsq")
+
+
+def gen_deep_modules(which=("phosphorus", "forced")):
+    """the benchmarked depth (416 levels: seven per lane) on a narrow grid, the reference's own year included: what
+    tests/test_gpu_oracle_deep_modules.py and the 416 case of test_phosphorus_other_instantiations hold the device to,
+    and what pins the oracle itself at that depth (test_oracle_phosphorus.py, test_oracle_forced_file.py)"""
+    if "phosphorus" in which:
+        # (two time samples: a Jacobian of 4992 unknowns is 200 KB, and the file stays near 600 KB)
+        gen_phosphorus("416x4", 416, 4, 14, with_fcn=True, times=(0.3, 0.66))
+    if "forced" in which:
+        # every kind-2 feature at once: file restoring, file source, sink threshold
+        gen_forced_file("file_sink_thres_416x4", 416, 4, "file", "file", 0.5, 15, with_fcn=True)
 
 
 def gen_forced_file_all():
@@ -436,6 +453,9 @@ def main():
     sys.path.insert(0, REF)
     if len(sys.argv) == 4 and sys.argv[1] == "large":     # large <n> <ref|sched|merge>
         gen_comp_fcn_large(int(sys.argv[2]), sys.argv[3])
+        return
+    if sys.argv[1:2] == ["deep_modules"] and len(sys.argv) <= 3:      # only the fixtures at seven levels per lane
+        gen_deep_modules(tuple(sys.argv[2:]) or ("phosphorus", "forced"))
         return
     if sys.argv[1:] == ["forced_file"]:      # only the fixtures of the file-driven forced options
         gen_forced_file_all()

@@ -37,15 +37,35 @@ def free_years(eng, x, **kw):
     return faithful, eng.comp_fcn(x, **kw)
 
 
+def oracle_module(nz, ny, module=None):
+    """the oracle's tracer module on the default nz x ny grid from a picklable description: None (iage), or a dict with
+    "kind" ("iage", "phosphorus", "forced"), "params" (keyword arguments of the module: the phosphorus parameters, the
+    options of oracle.model.Forced) and "forcing" (the (times, values) series of the file-driven forced options, by keyword)"""
+    from oracle.model import Forced, Phosphorus
+
+    model, iage = oracle_iage(nz, ny)
+    kind = "iage" if module is None else module["kind"]
+    params = {} if module is None else dict(module.get("params") or {})
+    forcing = {} if module is None else dict(module.get("forcing") or {})
+    if kind == "iage":
+        return iage
+    if kind == "phosphorus":
+        return Phosphorus(model, **params)
+    if kind == "forced":
+        return Forced(model, **params, **{name: (np.asarray(t), np.asarray(v)) for name, (t, v) in forcing.items()})
+    raise ValueError(f"unknown oracle module kind {kind!r}")
+
+
 def oracle_year_job(args):
     """one CPU year of the oracle on one BLAS thread, for worker processes of the parity tests (spawned: they never touch
-    the GPU): args = (nz, ny, x, rows) -- a replay of the accepted steps `rows` from x, or (rows None) a free-running year"""
+    the GPU): args = (nz, ny, x, rows[, module]) -- a replay of the accepted steps `rows` from x, or (rows None) a
+    free-running year; of iage, or of the module that `oracle_module` makes of the description `module`"""
     from threadpoolctl import threadpool_limits
 
     from oracle import radau
 
-    nz, ny, x, rows = args
-    _, tm = oracle_iage(nz, ny)
+    nz, ny, x, rows = args[:4]
+    tm = oracle_module(nz, ny, args[4] if len(args) > 4 else None)
     with threadpool_limits(limits=1):
         if rows is None:
             return radau.comp_fcn(tm, x)

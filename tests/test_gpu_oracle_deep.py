@@ -97,8 +97,11 @@ def deep():
         pool.join()
 
 
-def _record(key, value):
+def _record(key, value, fname=None):
+    """one figure into the margins file of this module -- or into `fname` beside it (test_gpu_oracle_deep_modules.py)"""
     path = os.path.join(ROOT, "gpurun_out", "r04_oracle_deep_margins.json")
+    if fname is not None:
+        path = os.path.join(os.path.dirname(path), fname)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     data = {}
     if os.path.exists(path):

@@ -26,7 +26,7 @@ def _setup(golden_dir, tag, **kwargs):
     return g, eng, Phosphorus(Py2dModel(depth, ypos))
 
 
-@pytest.mark.parametrize("tag", ["22x9", "70x12"])
+@pytest.mark.parametrize("tag", ["22x9", "70x12", "416x4"])
 def test_phosphorus_tend_and_jacobian(golden_dir, tag):
     g, eng, tm = _setup(golden_dir, tag)
     yd = eng.upload(g["y"])
@@ -308,10 +308,12 @@ def test_phosphorus_newton_resume(tmp_path):
     ModelState.reset_class()
 
 
-@pytest.mark.parametrize("nz", [130, 200, 300, 384, 512])
-def test_phosphorus_other_instantiations(nz):
-    """the phosphorus kernels at other levels-per-lane counts (E = 3, 4, 5, 6, 8): tendency, J v
-    and the coupled shifted solves against the oracle"""
+@pytest.mark.parametrize("nz", [130, 200, 300, 384, 385, 416, 448, 512])
+def test_phosphorus_other_instantiations(golden_dir, nz):
+    """the phosphorus kernels at other levels-per-lane counts (E = 3, 4, 5, 6, 7, 8): tendency, J v
+    and the coupled shifted solves against the oracle.  E = 7 is what bench.py's module mix runs: the first level of
+    the seventh group (385), the benchmarked depth (416: the tendency also against the reference's own, from
+    phosphorus_416x4.npz, to the bound of test_phosphorus_tend_and_jacobian) and the full group (448)"""
     from nk_ooc_amd.engine import phosphorus_engine
     from nk_ooc_amd.grid import Grid2d
 
@@ -340,3 +342,10 @@ def test_phosphorus_other_instantiations(nz):
     want = spsolve(((radau.MU_COMPLEX / h) * identity(n, format="csc") - jac).astype(complex), v + 1j * v2)
     x_re, x_im, _ = eng.shifted_solve(t, h, radau.MU_COMPLEX, eng.upload(v), eng.upload(v2))
     assert rel_err(eng.download(x_re).reshape(-1) + 1j * eng.download(x_im).reshape(-1), want) < 1e-9
+    if nz == 416:
+        g = np.load(f"{golden_dir}/phosphorus_416x4.npz")
+        assert (int(g["nz"]), int(g["ny"])) == (nz, ny)
+        yg = eng.upload(g["y"])
+        for i, tg in enumerate(g["times"]):
+            got = eng.download(eng.tend(tg, yg)).reshape(-1)
+            assert np.max(np.abs(got - g["tend"][i])) <= 4e-16 * np.max(np.abs(g["tend"][i]))

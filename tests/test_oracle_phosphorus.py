@@ -16,7 +16,7 @@ def _module(nz, ny):
     return Phosphorus(Py2dModel(depth, ypos)), depth, ypos
 
 
-@pytest.mark.parametrize("tag", ["22x9", "70x12"])
+@pytest.mark.parametrize("tag", ["22x9", "70x12", "416x4"])
 def test_tend_and_jacobian_bitwise(golden_dir, tag):
     g = np.load(f"{golden_dir}/phosphorus_{tag}.npz")
     tm, _, _ = _module(int(g["nz"]), int(g["ny"]))
@@ -32,6 +32,17 @@ def test_tend_and_jacobian_bitwise(golden_dir, tag):
 def test_forward_year_bitwise(golden_dir):
     g = np.load(f"{golden_dir}/phosphorus_22x9.npz")
     tm, _, _ = _module(22, 9)
+    res, solver = radau.comp_fcn(tm, g["y0"], return_solver=True)
+    assert np.array_equal(res, g["fcn"])
+    assert (solver.stats.nfev, solver.stats.njev, solver.stats.nlu) == (int(g["nfev"]), int(g["njev"]), int(g["nlu"]))
+
+
+@pytest.mark.slow
+def test_forward_year_bitwise_seven_levels_per_lane(golden_dir):
+    """416 x 4 (the depth bench.py runs phosphorus at): the oracle's year is the reference's before the device is held to
+    it in test_gpu_oracle_deep_modules.py (four minutes of one core)"""
+    g = np.load(f"{golden_dir}/phosphorus_416x4.npz")
+    tm, _, _ = _module(int(g["nz"]), int(g["ny"]))
     res, solver = radau.comp_fcn(tm, g["y0"], return_solver=True)
     assert np.array_equal(res, g["fcn"])
     assert (solver.stats.nfev, solver.stats.njev, solver.stats.nlu) == (int(g["nfev"]), int(g["njev"]), int(g["nlu"]))
