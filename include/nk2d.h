@@ -372,6 +372,18 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    the resident kernel that fits two waves to a SIMD -- 256 registers, the rest in scratch memory -- where that lets every
    (tracer, ypos) column be resident instead of several rounds of columns per command, 416 x 416: 1 248 columns; 2: wherever
    that flavour exists; 0: never.  Counters "stream_two_waves_kernel", "stream_columns_per_workgroup"),
+   "stream_hist" (0, default, or 1; opt-in: the samples of nk2d_comp_fcn_hist in a year that runs as a command stream are
+   COMMANDS of its resident kernel -- the dense output of the accepted step, packed, into a slot of a sample buffer in HBM,
+   pushed right behind the step's boundary command, which such a step keeps -- instead of ending the kernel for a piece of
+   launches and a device-to-host copy per sample; the host unpacks and copies the buffered samples out when the slots are
+   full and after the year's end.  A step that has no fused boundary command samples by launches as before -- the year's
+   last step always; otherwise only a step whose t + h rounds off t_new or whose successor's step size is not a positive
+   number -- and is not counted.  The same samples and the same year bit for bit; a year whose kernel gives up is rerun by
+   launches, samples included, and books nothing in the two counters below),
+   "stream_hist_mb" (>= 0, default 256: budget of that sample buffer in MiB; it holds
+   clamp(floor(budget / bytes of a packed state), 1, samples of the year) slots, 0 means a single slot.  Counters
+   "stream_hist_samples": samples produced by a command and delivered, "stream_hist_drains": times the buffer was emptied --
+   both booked when a year has run as a stream to its end),
    "device_ctl" (only 0: rounds 1 - 3 had device-side controllers 1, 2, 3; they lost to the command stream and are gone),
    "spec_bias" (default 1: what the host queues behind a Newton iteration it has not judged yet -- the next iteration, or the
    error estimate when the predicted convergence test value is below this many tolerances; never a decision; measured flat),

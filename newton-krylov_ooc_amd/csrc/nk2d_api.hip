@@ -187,6 +187,17 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
         c->frozen_tape = (int)value;
         return 0;
     }
+    if (key == "stream_hist") {
+        // history samples as commands of the year's resident kernel (nk2d_stream.h, NK2D_OP_DENSE_OUT) instead of launches
+        if (value != 0.0 && value != 1.0) return nk2d_fail(c, "nk2d_set_option: stream_hist is 0 or 1");
+        c->stream_hist = (int)value;
+        return 0;
+    }
+    if (key == "stream_hist_mb") {
+        if (!(value >= 0.0) || !std::isfinite(value)) return nk2d_fail(c, "nk2d_set_option: stream_hist_mb must be >= 0");
+        c->stream_hist_mb = value;
+        return 0;
+    }
     if (key == "stream_two_waves") {
         // (decides the shape of the resident kernel: taken before the context's first year as a command stream)
         if (c->strm) return nk2d_fail(c, "nk2d_set_option: stream_two_waves must be set before the first year of the context");
@@ -582,6 +593,12 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->hist_next = 0;
     c->hist_t = nullptr;
     c->hist_host = nullptr;
+    c->stream_hist = 0;
+    c->stream_hist_mb = 256.0;
+    c->HISTBUF = nullptr;
+    c->hist_slots = c->hist_buf_elems = 0;
+    c->hist_year_samples = c->hist_year_drains = 0;
+    c->stream_hist_samples = c->stream_hist_drains = 0;
     c->sweep_wpb = 4;
     NK2D_CHECK(c, hipHostMalloc((void**)&c->hRED, sizeof(double) * 4096));
     NK2D_CHECK(c, hipHostMalloc((void**)&c->hPART, sizeof(double) * c->ncol));
@@ -713,7 +730,7 @@ extern "C" void nk2d_destroy(nk2d_ctx* c) {
                       c->XCR[1], c->XCI[0], c->XCI[1], c->TMP, c->TMP2, c->PART, c->PART2, c->STEP_NORM, c->STEP_PART, c->RED, c->STAGE, c->RCOEF,
                       c->FR_INV, c->FC_INVR, c->FC_INVI, c->FR_TAB, c->FC_TABR, c->FC_TABI,
                       c->LIGHT, c->UPR, c->YLIN,
-                      c->SMSREC, c->RESTREC};
+                      c->SMSREC, c->RESTREC, c->HISTBUF};
     for (double* b : bufs)
         if (b) (void)hipFree(b);
     delete[] c->sms_t;
@@ -1061,6 +1078,8 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "stream_timeouts") v = c->stream_timeouts;
     else if (key == "stream_columns_per_workgroup") v = nk2d_stream_columns_per_workgroup(c);
     else if (key == "stream_two_waves_kernel") v = nk2d_stream_two_waves(c);
+    else if (key == "stream_hist_samples") v = c->stream_hist_samples;
+    else if (key == "stream_hist_drains") v = c->stream_hist_drains;
     else if (key == "tape_years_run") v = c->tape_years_run;
     else if (key == "tape_builds") v = c->tape_builds;
     else if (key == "tape_timeouts") v = c->tape_timeouts;
@@ -1113,9 +1132,8 @@ extern "C" int nk2d_set_frozen_schedule(nk2d_ctx* c, const double* sched, int64_
 // evaluated with the dense output of the step just taken)
 int nk2d_hist_sample(nk2d_ctx* c, double t_old, double t_new, bool first) {
     const size_t n = (size_t)c->tc * c->nz * c->ny;
-    while (c->hist_next < c->hist_n && c->hist_t[c->hist_next] <= t_new) {
-        const double te = c->hist_t[c->hist_next];
-        const double x = (te - t_old) / (t_new - t_old);
+    double x = 0.0;
+    while (nk2d_hist_due(c, t_old, t_new, &x)) {
         NK2D_TRY(nk2d_r_dense(c, x, c->TMP));
         NK2D_TRY(ensure_stage(c, n));
         NK2D_TRY(nk2d_k_unpack_state(c, c->TMP, c->STAGE));
@@ -1123,6 +1141,67 @@ int nk2d_hist_sample(nk2d_ctx* c, double t_old, double t_new, bool first) {
         c->hist_next++;
     }
     (void)first;
+    return 0;
+}
+
+// ---- option "stream_hist": the samples of a year that runs as a command stream are commands of its resident kernel ----
+// The sample buffer: nslots = clamp(floor(stream_hist_mb MiB / (nv 8)), 1, hist_n) packed samples, allocated before the
+// first sampled stream year (no kernel is resident then: freeing memory waits for the device), kept, grown when needed.
+int nk2d_hist_buf_ready(nk2d_ctx* c) {
+    nk2d_hist_buf_reset(c);
+    const double bytes = c->stream_hist_mb * 1048576.0;
+    const double fit = std::floor(bytes / (8.0 * (double)c->nv));
+    c->hist_slots = (size_t)std::min((double)c->hist_n, std::max(1.0, fit));
+    const size_t need = c->hist_slots * c->nv;
+    if (c->hist_buf_elems < need) {
+        NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+        if (c->HISTBUF) NK2D_CHECK(c, hipFree(c->HISTBUF));
+        c->HISTBUF = nullptr;
+        c->hist_buf_elems = 0;
+        NK2D_CHECK(c, hipMalloc((void**)&c->HISTBUF, sizeof(double) * need));
+        c->hist_buf_elems = need;
+    }
+    return ensure_stage(c, (size_t)c->tc * c->nz * c->ny);
+}
+
+// a year that starts or is given up (the kernel lost: rerun by launches): nothing buffered, nothing of it booked -- the
+// counters take a year's samples and drains when it has run as a stream to its end (nk2d_hist_year_done)
+void nk2d_hist_buf_reset(nk2d_ctx* c) {
+    c->hist_slot_k.clear();
+    c->hist_year_samples = c->hist_year_drains = 0;
+}
+void nk2d_hist_year_done(nk2d_ctx* c) {
+    c->stream_hist_samples += c->hist_year_samples;
+    c->stream_hist_drains += c->hist_year_drains;
+    c->hist_year_samples = c->hist_year_drains = 0;
+}
+
+// every buffered sample, in the order of the slots: unpack -> STAGE -> pinned twin -> the caller's array.  Launches and
+// copies on the context's stream, behind the resident kernel (which the first of them tells to finish).
+int nk2d_hist_drain(nk2d_ctx* c) {
+    if (c->hist_slot_k.empty()) return 0;
+    const size_t n = (size_t)c->tc * c->nz * c->ny;
+    NK2D_TRY(ensure_stage(c, n));
+    for (size_t slot = 0; slot < c->hist_slot_k.size(); ++slot) {
+        NK2D_TRY(nk2d_k_unpack_state(c, c->HISTBUF + slot * c->nv, c->STAGE));
+        NK2D_TRY(stage_out(c, c->hist_host + (size_t)c->hist_slot_k[slot] * n, n));
+    }
+    c->hist_year_samples += (int64_t)c->hist_slot_k.size();
+    c->hist_year_drains++;
+    c->hist_slot_k.clear();
+    return 0;
+}
+
+// the samples due at t_new, right behind the boundary command of the accepted step (t_old, t_new): after the boundary's
+// pointer swaps YOLD is the step's old state and ZP its Z, and nothing writes them before the next boundary
+int nk2d_hist_push(nk2d_ctx* c, double t_old, double t_new) {
+    double x = 0.0;
+    while (nk2d_hist_due(c, t_old, t_new, &x)) {
+        if (c->hist_slot_k.size() >= c->hist_slots) NK2D_TRY(nk2d_hist_drain(c));
+        NK2D_TRY(nk2d_r_dense_push(c, x, c->HISTBUF + c->hist_slot_k.size() * c->nv));
+        c->hist_slot_k.push_back(c->hist_next);
+        c->hist_next++;
+    }
     return 0;
 }
 
@@ -1137,8 +1216,10 @@ extern "C" int nk2d_comp_fcn_hist(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, nk2d_sta
     c->hist_next = 0;
     c->hist_t = t_eval;
     c->hist_host = host_hist;
+    nk2d_hist_buf_reset(c);
     const int rc = nk2d_radau_year(c, x, fx, stats, nullptr, 0, nullptr, 0, nullptr);
-    const bool complete = c->hist_next == n_eval;
+    const bool complete = c->hist_next == n_eval && c->hist_slot_k.empty();
+    nk2d_hist_buf_reset(c);
     c->hist_n = 0;
     c->hist_t = nullptr;
     c->hist_host = nullptr;

@@ -1630,6 +1630,28 @@ __device__ __forceinline__ void err_rhs_body(const double* __restrict__ f, const
     store_col<E>(out, task, lane, ff);
 }
 
+// dense output y(t) = y_old + Q [x, x^2, x^3], Q = Z^T P  (radau.py:557-570), for t_eval samples: the launch k_dense and
+// the command NK2D_OP_DENSE_OUT (WT = 1: write-through, as every command of the resident kernel)
+template <int E, int WT = 0>
+__device__ __forceinline__ void dense_body(const double* __restrict__ yold, const double* __restrict__ zp, size_t nv,
+                                           double x, double* __restrict__ out, int task, int lane) {
+    double yo[E], z0[E], z1[E], z2[E];
+    load_col<E, WT>(yold, task, lane, yo);
+    load_col<E, WT>(zp, task, lane, z0);
+    load_col<E, WT>(zp + nv, task, lane, z1);
+    load_col<E, WT>(zp + 2 * nv, task, lane, z2);
+    const double p1 = x, p2 = p1 * x, p3 = p2 * x;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        double q[3];
+#pragma unroll
+        for (int cidx = 0; cidx < 3; ++cidx) q[cidx] = (z0[e] * cP[0][cidx] + z1[e] * cP[1][cidx]) + z2[e] * cP[2][cidx];
+        double v = (q[0] * p1 + q[1] * p2) + q[2] * p3;
+        yo[e] = v + yo[e];
+    }
+    store_col<E, WT>(out, task, lane, yo);
+}
+
 // ---------------------------------------------------------------------------------
 // Fused error estimate (radau.py:477-481) for solves of at most two sweeps:
 //   launch 0: right-hand side f + Z^T E / h formed in registers, first line sweep (no lateral

@@ -196,6 +196,15 @@ struct nk2d_ctx {
     int hist_n, hist_next;
     const double* hist_t;
     double* hist_host;   // [hist_n][tc][nz][ny]
+    // ... as commands of the year's resident kernel (option "stream_hist", nk2d_stream.h: NK2D_OP_DENSE_OUT): packed samples
+    // wait in the slots of a buffer in HBM until the kernel has ended (the slots are full; the end of the year)
+    int stream_hist;             // option "stream_hist": 0 (default) a sampled step is a piece of launches, 1 its samples are commands
+    double stream_hist_mb;       // option "stream_hist_mb": budget of the sample buffer in MiB (0: one slot)
+    double* HISTBUF;             // [hist_slots][nv]
+    size_t hist_slots, hist_buf_elems;   // slots of this year, doubles allocated
+    std::vector<int> hist_slot_k;        // the sample each filled slot holds, in the order they were filled
+    int64_t hist_year_samples, hist_year_drains;   // what the running year has drained so far: booked when the year stands
+    int64_t stream_hist_samples, stream_hist_drains;   // counters (nk2d_get_counter): years that ran as streams to their end
 
     // counters of the running comp_fcn
     nk2d_stats st;
@@ -645,6 +654,22 @@ int nk2d_r_final(nk2d_ctx* c, const double* y0, double* out);
 int nk2d_r_dense(nk2d_ctx* c, double x, double* out);
 // nk2d_radau.hip
 int nk2d_hist_sample(nk2d_ctx* c, double t_old, double t_new, bool first);
+// the next sample of the running year if it is due in the accepted step (t_old, t_new), and its dense-output abscissa: ONE
+// expression for the samples by launches (nk2d_hist_sample) and by commands (nk2d_hist_push) -- they must give the same bits
+static inline bool nk2d_hist_due(const nk2d_ctx* c, double t_old, double t_new, double* x) {
+    if (!(c->hist_next < c->hist_n && c->hist_t[c->hist_next] <= t_new)) return false;
+    const double te = c->hist_t[c->hist_next];
+    *x = (te - t_old) / (t_new - t_old);
+    return true;
+}
+// option "stream_hist": the sample buffer in place before the year; the samples due at t_new as commands; the buffered
+// samples to the host (launches: ends a running kernel); the bookkeeping of a year that is given up
+int nk2d_hist_buf_ready(nk2d_ctx* c);
+int nk2d_hist_push(nk2d_ctx* c, double t_old, double t_new);
+int nk2d_hist_drain(nk2d_ctx* c);
+void nk2d_hist_buf_reset(nk2d_ctx* c);
+void nk2d_hist_year_done(nk2d_ctx* c);
+int nk2d_r_dense_push(nk2d_ctx* c, double x, double* out);
 int nk2d_radau_year(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, nk2d_stats* stats, const double* replay,
                     int64_t replay_n, double* record, int64_t record_cap, int64_t* record_n, bool replay_own = false);
 // nk2d_precond.hip

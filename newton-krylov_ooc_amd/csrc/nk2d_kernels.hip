@@ -658,21 +658,7 @@ template <int E>
 __global__ void k_dense(int ncol, const double* __restrict__ yold, const double* __restrict__ zp, size_t nv, double x,
                         double* __restrict__ out) {
     TASK_PROLOGUE(ncol)
-    double yo[E], z0[E], z1[E], z2[E];
-    load_col<E>(yold, task, lane, yo);
-    load_col<E>(zp, task, lane, z0);
-    load_col<E>(zp + nv, task, lane, z1);
-    load_col<E>(zp + 2 * nv, task, lane, z2);
-    const double p1 = x, p2 = p1 * x, p3 = p2 * x;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        double q[3];
-#pragma unroll
-        for (int cidx = 0; cidx < 3; ++cidx) q[cidx] = (z0[e] * cP[0][cidx] + z1[e] * cP[1][cidx]) + z2[e] * cP[2][cidx];
-        double v = (q[0] * p1 + q[1] * p2) + q[2] * p3;
-        yo[e] = v + yo[e];
-    }
-    store_col<E>(out, task, lane, yo);
+    dense_body<E, 0>(yold, zp, nv, x, out, task, lane);
 }
 
 int nk2d_r_dense(nk2d_ctx* c, double x, double* out) {
@@ -681,6 +667,13 @@ int nk2d_r_dense(nk2d_ctx* c, double x, double* out) {
     NK2D_CHECK(c, hipGetLastError());
     c->st.nlaunch++;
     return 0;
+}
+// the same as a command of the year's resident kernel (option "stream_hist"): packed, into a slot of the sample buffer
+int nk2d_r_dense_push(nk2d_ctx* c, double x, double* out) {
+    StreamCmd cmd = {};
+    cmd.op = NK2D_OP_DENSE_OUT;
+    cmd.u.dn.yold = c->YOLD; cmd.u.dn.zp = c->ZP; cmd.u.dn.nv = c->nv; cmd.u.dn.x = x; cmd.u.dn.out = out;
+    return nk2d_stream_push(c, cmd, false);
 }
 int nk2d_r_predict(nk2d_ctx* c, double x0, double x1, double x2) {
     PredictArgs A = predict_args(c, x0, x1, x2);

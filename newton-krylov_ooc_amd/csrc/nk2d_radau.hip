@@ -616,9 +616,13 @@ int run_free(Ctl& s, double* record, int64_t record_cap, int64_t* record_n) {
         // device-side controllers keep the separate launches.
         const bool jac_due = recompute_jac || c->jac_fresh;
         const bool jac_needs_state = c->kind == 1 || (c->kind == 2 && c->d.sms_nrec > 0 && c->d.sink_thres > 0.0);
-        // (a year with history samples: only the steps that hold a sample time keep the separate launches)
+        // (a year with history samples: only the steps that hold a sample time keep the separate launches -- or, where the
+        // samples are commands of the resident kernel behind the boundary command, option "stream_hist", none but the steps
+        // that cannot have a fused boundary anyway: the year's last, and one whose t + h rounds off t_new or whose successor's
+        // step size is not a positive number -- their samples go by launches, straight to the caller's array)
         const bool sample_due = c->hist_n > 0 && c->hist_next < c->hist_n && c->hist_t[c->hist_next] <= t_new;
-        bool fused = !sample_due && t + h == t_new && t_new < s.t1;
+        const bool sample_cmds = c->stream_hist && c->stream_on && c->hist_n > 0;
+        bool fused = (!sample_due || sample_cmds) && t + h == t_new && t_new < s.t1;
         double h2 = 0.0;
         if (fused) {
             // the next step's first attempt, as the top of this loop will compute it
@@ -665,6 +669,8 @@ int run_free(Ctl& s, double* record, int64_t record_cap, int64_t* record_n) {
             } else {
                 s.current_jac = false;
             }
+            // the samples of this step: YOLD and ZP are its old state and its Z now, until the next boundary
+            if (sample_due && sample_cmds) NK2D_TRY(nk2d_hist_push(c, t, t_new));
         } else {
             if (t + h == t_new) std::swap(c->KV[3], c->KV[2]);  // stage-3 plane is the plane at t_new
             else NK2D_TRY(eval_kv(c, t_new, 3));
@@ -1372,6 +1378,8 @@ int nk2d_radau_year(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, nk2d_stats* stats, con
                 }
             } stream_guard{c};
             if (as_stream) NK2D_TRY(nk2d_stream_ready(c));
+            const bool sample_cmds = as_stream && c->stream_hist && c->hist_n > 0;
+            if (sample_cmds) NK2D_TRY(nk2d_hist_buf_ready(c));
             c->stream_on = as_stream ? 1 : 0;
             int frc = run_free(s, record, record_cap, record_n);
             c->stream_on = 0;
@@ -1379,6 +1387,11 @@ int nk2d_radau_year(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, nk2d_stats* stats, con
                 const int erc = nk2d_stream_end(c);
                 if (erc != 0 && erc != NK2D_RC_STREAM_LOST) return erc;
                 if (erc == NK2D_RC_STREAM_LOST) frc = NK2D_RC_STREAM_LOST;
+            }
+            // (the samples that wait in the buffer, now that the kernel has ended; those of a lost year are dropped below)
+            if (sample_cmds && frc == 0) {
+                NK2D_TRY(nk2d_hist_drain(c));
+                nk2d_hist_year_done(c);
             }
             if (frc == NK2D_RC_STREAM_LOST) {
                 if (++c->stream_lost >= 2) c->stream_years = 0;     // (not a third time on this context)
@@ -1388,7 +1401,7 @@ int nk2d_radau_year(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, nk2d_stats* stats, con
                 s.t = c->d.t0;
                 s.have_lu = false; s.have_dense = false; s.pre_setup = false;
                 s.has_old_h = s.has_old_err = false;
-                if (c->hist_n > 0) c->hist_next = 0;
+                if (c->hist_n > 0) { c->hist_next = 0; nk2d_hist_buf_reset(c); }
                 NK2D_TRY(start_year());
                 frc = run_free(s, record, record_cap, record_n);
             } else if (frc == 0 && as_stream) {

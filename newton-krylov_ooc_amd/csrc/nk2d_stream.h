@@ -11,8 +11,10 @@
 // iteration or the error estimate queued before the verdict on this one) and its roll-back by pointer swap: it pushes
 // commands into a ring in pinned host memory, a relay wave of the kernel copies them into HBM, and the per-column norm
 // partials come back through pinned host memory with a completion stamp per workgroup -- no launch, no event, no
-// stream synchronisation inside a year.  Whatever has no command (history samples, the rare several-sweep error
-// estimates) ends the kernel, runs as ordinary launches and the next command starts the kernel again.
+// stream synchronisation inside a year.  Whatever has no command ends the kernel, runs as ordinary launches and the next
+// command starts the kernel again.  History samples have one with option "stream_hist" (NK2D_OP_DENSE_OUT: the dense output
+// of the step just taken, packed, into a slot of a sample buffer in HBM that the host unpacks and copies out once the
+// kernel has ended); without the option a sampled step is such a piece of launches, as the year's last step always is.
 #pragma once
 
 #include "nk2d_bodies.h"
@@ -25,7 +27,9 @@ enum { NK2D_OP_EXIT = 1, NK2D_OP_SETUP = 2, NK2D_OP_NEWTON = 3, NK2D_OP_ERR = 4,
        // the launch that ends the last Newton iteration of a frozen step and the step (nk2d_r_newton_final)
        NK2D_OP_NEWTON_FINAL = 11,
        // Jacobian planes from a mixing plane in memory (nk2d_k_jac: modules whose Jacobian reads the state)
-       NK2D_OP_JAC = 12 };
+       NK2D_OP_JAC = 12,
+       // a history sample: the dense output of the step just taken (nk2d_r_dense), packed, column by column
+       NK2D_OP_DENSE_OUT = 13 };
 #define NK2D_CMD_NOTIFY 1   /* the host waits for this command: completion stamp of every workgroup to pinned memory */
 #define NK2D_CMD_FACTOR 2   /* OP_NEWTON: the launch that computes the line factorisation of its column (first after an "LU" event) */
 
@@ -51,6 +55,12 @@ struct StreamJac {          // nk2d_k_jac
     const double* ylin;
     double* UPR;
 };
+struct StreamDense {        // nk2d_r_dense
+    const double *yold, *zp;
+    size_t nv;
+    double x;
+    double* out;
+};
 struct StreamFinal {        // nk2d_r_newton_final
     FusedArgs nf;
     FinalArgs fin;
@@ -64,6 +74,7 @@ struct StreamCmd {
         StreamJac jac;
         SweepArgs sw;       // nk2d_k_sweep
         StreamColumns col;
+        StreamDense dn;
         FusedArgs nf;       // nk2d_r_newton_fused
         ErrArgs err;        // one launch of nk2d_r_err_fused
         StreamSetup su;

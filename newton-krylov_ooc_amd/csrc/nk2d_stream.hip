@@ -328,6 +328,10 @@ __device__ __forceinline__ void stream_body(const DevP& P, const StreamArgs& A) 
                         store_col<E, 1>(S.out, task, lane, v);
                     }
                 }
+        } else if (op == NK2D_OP_DENSE_OUT) {
+            const StreamDense& S = cmd.u.dn;
+            for (int tr = tw; tr < P.tc; tr += nw)
+                for (int j = j0; j < j1; ++j) dense_body<E, 1>(S.yold, S.zp, S.nv, S.x, S.out, tr * P.ny + j, lane);
         }
         // ---- hand-over: every wave has drained its write-through stores, the workgroup publishes the command it has
         // completed (and, where the host waits for it, stamps pinned memory), waits for its two lateral neighbours and
@@ -608,6 +612,7 @@ static int cmd_dwords(int op) {
         case NK2D_OP_SWEEP: body = sizeof(SweepArgs); break;
         case NK2D_OP_NEWTON_FINAL: body = sizeof(StreamFinal); break;
         case NK2D_OP_JAC: body = sizeof(StreamJac); break;
+        case NK2D_OP_DENSE_OUT: body = sizeof(StreamDense); break;
         case NK2D_OP_EXIT: body = 0; break;
         default: body = sizeof(StreamColumns); break;
     }

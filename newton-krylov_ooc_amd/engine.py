@@ -207,6 +207,11 @@ class ModuleEngine:
             self.set_option("stream_years", float(os.environ["NK2D_STREAM_YEARS"]))
         if "NK2D_FROZEN_TAPE" in os.environ:
             self.set_option("frozen_tape", float(os.environ["NK2D_FROZEN_TAPE"]))
+        # history samples as commands of the year's resident kernel (csrc/nk2d_stream.h), and their buffer's budget in MiB
+        if "NK2D_STREAM_HIST" in os.environ:
+            self.set_option("stream_hist", float(os.environ["NK2D_STREAM_HIST"]))
+        if "NK2D_STREAM_HIST_MB" in os.environ:
+            self.set_option("stream_hist_mb", float(os.environ["NK2D_STREAM_HIST_MB"]))
         self.set_option("jac_fresh", float(os.environ.get("NK2D_JAC_FRESH", DEFAULT_JAC_FRESH)))
         self.set_option("growth_cap", float(os.environ.get("NK2D_GROWTH_CAP", DEFAULT_GROWTH_CAP)))
         self.set_option("jac_stage", float(os.environ.get("NK2D_JAC_STAGE", DEFAULT_JAC_STAGE)))
