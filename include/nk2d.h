@@ -225,7 +225,10 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    "frozen_team_years" (of them: a four-wave team per column), "frozen_cache_bytes",
    "frozen_launch_us" (device time of those launches), "frozen_cache_pending" (1 while a thread allocates a large cache),
    "frozen_cache_builds", "frozen_fallbacks", "frozen_resumes"; of the host-side controller: "spec_launches_dropped",
-   "spec_front_launches_dropped", "err_estimates_queued", "err_estimates_dropped" (work queued ahead of a verdict). */
+   "spec_front_launches_dropped", "err_estimates_queued", "err_estimates_dropped" (work queued ahead of a verdict); of the
+   preconditioner (option "pc_two_ended"): "pc_setup_rounds" (dependent inversion rounds of the last block elimination: ny,
+   or ny / 2 + 1 from both ends), "pc_sub_launches" (dependent mat-vec launches of the last block substitution: 2 ny - 1,
+   or at most ny + 2). */
 int nk2d_get_counter(nk2d_ctx* ctx, const char* name, int64_t* out);
 /* hash of everything a recorded schedule depends on besides the state: grid, module description, tolerances, the
    controller options (jac_fresh, jac_stage, lin_tol, min_sweeps, growth_cap, factor storage), the library version and a
@@ -424,7 +427,12 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    "hook_spec_depth" (1 or 2, default 2: whole Newton iterations a controller with a vector norm hook queues ahead of a verdict), "barrier_timeout_ms" (longest wait at a grid barrier of the one-launch years, default 2000:
    then the year is rerun launch by launch), "year_fences" (1: release / acquire fences around those barriers, validation),
    "pc_fp32" (1: the preconditioner's Schur inverses stored in single precision -- half the HBM -- and every apply refined
-   "pc_refine" times, default 1, against the exact block tridiagonal operator; set before nk2d_precond_setup) */
+   "pc_refine" times, default 1, against the exact block tridiagonal operator; set before nk2d_precond_setup),
+   "pc_two_ended" (0, default, or 1; opt-in: the preconditioner's block elimination runs from ypos = 0 and ypos = ny - 1 at
+   once -- two chains of half the length in the same launches, a twisted factorisation -- and meets in column ny / 2, and
+   the substitution advances both chains per launch.  Read by nk2d_precond_setup, nk2d_precond_setup_states and
+   nk2d_shift_factor; nk2d_precond_apply and nk2d_shift_solve follow the value of the set-up they use.  Composes with
+   "pc_fp32" and "pc_fused"; with "pc_valu" 1 the set-up is refused.  Counters "pc_setup_rounds", "pc_sub_launches") */
 int nk2d_set_option(nk2d_ctx* ctx, const char* name, double value);
 
 /* block until every operation queued on the context's stream has finished */

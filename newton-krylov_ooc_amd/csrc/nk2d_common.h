@@ -191,6 +191,8 @@ struct nk2d_ctx {
     int pc_valu;   // 1: the round-1 preconditioner kernels (VALU rank-32 update, 8-byte mat-vec loads), for A/B runs
     int pc_fp32;   // 1: Schur inverses of the linear modules' preconditioner stored in single precision (option "pc_fp32")
     int pc_refine; // ... with this many refinement steps per apply against the exact operator (option "pc_refine", default 1)
+    int pc_two_ended;   // option "pc_two_ended": 0 (default) the block elimination runs over ypos = 0 .. ny - 1, 1 from both ends at once (read at set-up; a factorisation keeps the value it was made with)
+    int64_t pc_setup_rounds, pc_sub_launches;   // counters (nk2d_get_counter): dependent inversion rounds of the last elimination, dependent mat-vec launches of the last substitution
 
     // optional dense-output sampling of the running comp_fcn (history files)
     int hist_n, hist_next;

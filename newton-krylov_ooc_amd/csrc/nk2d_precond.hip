@@ -46,6 +46,10 @@ struct Precond {
     double* RV;    // right-hand sides kept for the residual [tc][nb][m]
     double* X0;    // first solution [tc][nb][m]
     int fp32;
+    // option "pc_two_ended" as it was when this was factorised: the elimination ran from ypos = 0 and ypos = nb - 1 at once
+    // and met in column jm = nb / 2; slot j of SINV / SINV32 holds S_j^-1 (j < jm), Z^-1 (j = jm) or T_j^-1 (j > jm).  The
+    // Gauss-Jordan work buffers below and PREV then hold both chains of a round: twice the systems
+    int two_ended, jm;
     double* BUF;   // Gauss-Jordan ping-pong [2][tc][m][m]
     double* PINV;  // inverses of this and the next panel step's pivot block [2][tc][32][32] (k_pc_gj_step)
     double* ROWS;  // scaled pivot rows    [tc][NB][m]
@@ -145,6 +149,59 @@ __global__ void k_pc_schur(PcDev P, int j, const double* __restrict__ sinv_prev,
         val = val - (l * sinv_prev[(size_t)tr * prev_sys_stride + (size_t)r * P.m + c]) * u;
     }
     out[((size_t)tr * P.m + r) * P.m + c] = val;
+}
+
+// entry (r, c) of the diagonal block D_j of system tr (mode 0: the tracer, mode 1: the shift), as k_pc_schur forms it
+__device__ __forceinline__ double pc_block_entry(const PcDev& P, int tr, int j, int tau, int k, int tc_, int kc) {
+    double val = 0.0;
+    if (P.mode == 1) {
+        val = shifted_entry(P, tr, j, tau, k, tc_, kc);
+    } else if (tc_ == tau) {
+        if (kc == k) {
+            double jc = pj(P, tau, PL_C, k, j) - P.decay[tr];
+            if (k == 0) jc = jc - P.surf[tr];
+            if (P.kind == 2) jc = jc - pj(P, tau, PL_UPR, k, j);   // sink threshold of the forced module
+            val = 1.0 - P.dt * jc;
+        } else if (kc == k - 1) {
+            val = -(P.dt * pj(P, tau, PL_L, k, j));
+        } else if (kc == k + 1) {
+            val = -(P.dt * pj(P, tau, PL_U, k, j));
+        }
+    } else if (kc == k && tc_ == (tau + P.nt - 1) % P.nt) {
+        val = -1.0;
+    }
+    return val;
+}
+
+// The same for the elimination from both ends of the ypos axis (option "pc_two_ended"): the systems of a launch are one or
+// two groups of nsys (blockIdx.z / nsys), each with its column j and the inverses it is corrected with --
+//   lo: the inverse of the block of column j - 1, left chain   S_j = D_j - diag(l_j) S_{j-1}^-1 diag(u_{j-1})
+//   hi: the inverse of the block of column j + 1, right chain  T_j = D_j - diag(u_j) T_{j+1}^-1 diag(l_{j+1})
+//   both: the block the chains meet in                         Z = (D_jm - diag(l) S^-1 diag(u)) - diag(u) T^-1 diag(l)
+// (the left term first: a fixed order); neither: the first block of a chain
+struct PcSchurEnd {
+    int j;
+    const double *lo, *hi;
+};
+
+__global__ void k_pc_schur_ends(PcDev P, int nsys, PcSchurEnd e0, PcSchurEnd e1, size_t prev_sys_stride,
+                                double* __restrict__ out) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = blockIdx.y;
+    const int z = blockIdx.z;
+    if (c >= P.m) return;
+    const bool second = z >= nsys;
+    const int tr = second ? z - nsys : z;
+    const int j = second ? e1.j : e0.j;
+    const double* lo = second ? e1.lo : e0.lo;
+    const double* hi = second ? e1.hi : e0.hi;
+    const int tau = r / P.nz, k = r - tau * P.nz;
+    const int tc_ = c / P.nz, kc = c - tc_ * P.nz;
+    double val = pc_block_entry(P, tr, j, tau, k, tc_, kc);
+    const size_t at = (size_t)tr * prev_sys_stride + (size_t)r * P.m + c;
+    if (lo) val = val - (lat_l(P, tau, k, j) * lo[at]) * lat_u(P, tc_, kc, j - 1);
+    if (hi) val = val - (lat_u(P, tau, k, j) * hi[at]) * lat_l(P, tc_, kc, j + 1);
+    out[((size_t)z * P.m + r) * P.m + c] = val;
 }
 
 // ---------------------------------------------------------------------------------
@@ -626,6 +683,44 @@ __global__ void __launch_bounds__(256) k_pc_gemv2(PcDev P, int mode, int j, cons
     }
 }
 
+// (the sum of the kernel above, for its two-ended twin below: this lane's share of the row row2 of m2 double2 times the
+// vector av2, which the whole workgroup stages in xs)
+__device__ __forceinline__ double pc_row_dot2(double2* xs, const double2* row2, const double2* av2, int m2, bool live, int lane) {
+    // the matrix row first (it comes from HBM), then the vector (L2)
+    double2 mv[PC_GEMV_CHUNK];
+#pragma unroll
+    for (int q = 0; q < PC_GEMV_CHUNK; ++q) {
+        const int c = lane + 64 * q;
+        mv[q] = (live && c < m2) ? row2[c] : make_double2(0.0, 0.0);
+    }
+    for (int i = threadIdx.x; i < m2; i += blockDim.x) xs[i] = av2[i];
+    __syncthreads();
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < PC_GEMV_CHUNK; ++q) {
+        const int c = lane + 64 * q;
+        const double2 xv = (c < m2) ? xs[c] : make_double2(0.0, 0.0);
+        acc[(2 * q) & 3] = __builtin_fma(mv[q].x, xv.x, acc[(2 * q) & 3]);
+        acc[(2 * q + 1) & 3] = __builtin_fma(mv[q].y, xv.y, acc[(2 * q + 1) & 3]);
+    }
+    for (int c0 = 64 * PC_GEMV_CHUNK; c0 < m2; c0 += 64 * PC_GEMV_CHUNK) {   // rows longer than one chunk
+        double2 mw[PC_GEMV_CHUNK];
+#pragma unroll
+        for (int q = 0; q < PC_GEMV_CHUNK; ++q) {
+            const int c = c0 + lane + 64 * q;
+            mw[q] = (live && c < m2) ? row2[c] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int q = 0; q < PC_GEMV_CHUNK; ++q) {
+            const int c = c0 + lane + 64 * q;
+            const double2 xv = (c < m2) ? xs[c] : make_double2(0.0, 0.0);
+            acc[(2 * q) & 3] = __builtin_fma(mw[q].x, xv.x, acc[(2 * q) & 3]);
+            acc[(2 * q + 1) & 3] = __builtin_fma(mw[q].y, xv.y, acc[(2 * q + 1) & 3]);
+        }
+    }
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+
 // dense mat-vec with the block-Thomas epilogues; one wave per row, eight 512-byte requests per wave in flight
 //   mode 0 (forward):  out[r] = rhs[r] - l[r] * sum_c M[r][c] a[c]
 //   mode 1 (backward): out[r] = x_j[r] = sum_c M[r][c] a[c], where a = y_j - U_j x_{j+1} was left behind by the
@@ -667,6 +762,24 @@ __global__ void __launch_bounds__(256) k_pc_gemv(PcDev P, int mode, int j, const
     }
 }
 
+// (the sum of the kernel above, for its two-ended twin below)
+__device__ __forceinline__ double pc_row_dot(const double* row, const double* av, int m, int lane) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c0 = lane; c0 < m; c0 += 512) {
+        double mv[8], xv[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int c = c0 + 64 * q;
+            const bool in = c < m;
+            mv[q] = in ? row[c] : 0.0;
+            xv[q] = in ? av[c] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q & 3] = __builtin_fma(mv[q], xv[q], acc[q & 3]);
+    }
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+
 // the same mat-vec on single precision matrices (option "pc_fp32"): 4-byte loads widened in registers, double precision
 // accumulation -- half the bytes of the stream that bounds an apply
 __global__ void __launch_bounds__(256) k_pc_gemv32(PcDev P, int mode, int j, const float* __restrict__ M,
@@ -704,6 +817,106 @@ __global__ void __launch_bounds__(256) k_pc_gemv32(PcDev P, int mode, int j, con
             if (prev) prev[at] = prev[at] - lat_u(P, slot, k, j - 1) * sum;
         }
     }
+}
+
+// (the sum of the kernel above, for its two-ended twin below)
+__device__ __forceinline__ double pc_row_dot32(const float* row, const double* av, int m, int lane) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c0 = lane; c0 < m; c0 += 1024) {
+        float mv[16];
+        double xv[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int c = c0 + 64 * q;
+            const bool in = c < m;
+            mv[q] = in ? row[c] : 0.0f;
+            xv[q] = in ? av[c] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[q & 3] = __builtin_fma((double)mv[q], xv[q], acc[q & 3]);
+    }
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+
+// ---------------------------------------------------------------------------------
+// The three mat-vecs for the substitution from both ends of the ypos axis (option "pc_two_ended"): blockIdx.z picks the
+// chain -- its matrix slot, vectors, column and lateral coupling -- so one launch advances both chains by a column.
+//   mode 0 (inward):  out[r] = rhs[r] - cpl[r] * sum_c M[r][c] a[c],  cpl = l_j (left chain: M = S_{j-1}^-1, a = y_{j-1})
+//                     or u_j (right chain, `up`: M = T_{j+1}^-1, a = y_{j+1}).  The block the chains meet in takes the
+//                     right chain's correction as that chain's last step (rhs = r_jm) and the left chain's in a launch of
+//                     its own behind it (rhs = out = y_jm, every row touches its own entry): a fixed order, no atomics
+//   mode 1 (outward): out[r] = x_j[r] = sum_c M[r][c] a[c]; the vectors the next launch reads are updated in place,
+//                     lo (column j - 1, towards ypos = 0):  lo[r] -= u_{j-1}[r] x_j[r]   (as mode 1 of the kernels above)
+//                     hi (column j + 1):                    hi[r] -= l_{j+1}[r] x_j[r]
+//                     the left chain has lo, the right chain hi, the meeting block both
+// The sums are those of the one-ended kernels, term for term.
+// ---------------------------------------------------------------------------------
+struct PcEnd {
+    int j, up;
+    size_t slot;            // offset of the chain's matrix inside a system of SINV / SINV32
+    const double *a, *rhs;
+    double *out, *lo, *hi;
+};
+
+__device__ __forceinline__ void pc_ends_epilogue(const PcDev& P, int mode, const PcEnd& e, int r, size_t at, double sum) {
+    const int slot = r / P.nz, k = r - slot * P.nz;
+    if (mode == 0) {
+        const double cpl = e.up ? lat_u(P, slot, k, e.j) : lat_l(P, slot, k, e.j);
+        e.out[at] = e.rhs[at] - cpl * sum;
+    } else {
+        e.out[at] = sum;
+        if (e.lo) e.lo[at] = e.lo[at] - lat_u(P, slot, k, e.j - 1) * sum;
+        if (e.hi) e.hi[at] = e.hi[at] - lat_l(P, slot, k, e.j + 1) * sum;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_pc_gemv2_ends(PcDev P, int mode, PcEnd e0, PcEnd e1, const double* __restrict__ M,
+                                                       size_t m_tr_stride, size_t v_tr_stride) {
+    __shared__ double2 xs[PC_GEMV_XMAX / 2];
+    const PcEnd e = blockIdx.z ? e1 : e0;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int tr = blockIdx.y;
+    const int m2 = P.m >> 1;
+    const double2* av2 = reinterpret_cast<const double2*>(e.a + (size_t)tr * v_tr_stride);
+    const bool live = r < P.m;
+    const double2* row2 = reinterpret_cast<const double2*>(M + (size_t)tr * m_tr_stride + e.slot + (size_t)(live ? r : 0) * P.m);
+    const double part = pc_row_dot2(xs, row2, av2, m2, live, lane);
+    if (!live) return;
+    const double sum = wave_sum(part);
+    if (lane == 0) pc_ends_epilogue(P, mode, e, r, (size_t)tr * v_tr_stride + r, sum);
+}
+
+__global__ void __launch_bounds__(256) k_pc_gemv_ends(PcDev P, int mode, PcEnd e0, PcEnd e1, const double* __restrict__ M,
+                                                      size_t m_tr_stride, size_t v_tr_stride) {
+    const PcEnd e = blockIdx.z ? e1 : e0;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int tr = blockIdx.y;
+    if (r >= P.m) return;
+    const double* row = M + (size_t)tr * m_tr_stride + e.slot + (size_t)r * P.m;
+    const double sum = wave_sum(pc_row_dot(row, e.a + (size_t)tr * v_tr_stride, P.m, lane));
+    if (lane == 0) pc_ends_epilogue(P, mode, e, r, (size_t)tr * v_tr_stride + r, sum);
+}
+
+__global__ void __launch_bounds__(256) k_pc_gemv32_ends(PcDev P, int mode, PcEnd e0, PcEnd e1, const float* __restrict__ M,
+                                                        size_t m_tr_stride, size_t v_tr_stride) {
+    const PcEnd e = blockIdx.z ? e1 : e0;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int tr = blockIdx.y;
+    if (r >= P.m) return;
+    const float* row = M + (size_t)tr * m_tr_stride + e.slot + (size_t)r * P.m;
+    const double sum = wave_sum(pc_row_dot32(row, e.a + (size_t)tr * v_tr_stride, P.m, lane));
+    if (lane == 0) pc_ends_epilogue(P, mode, e, r, (size_t)tr * v_tr_stride + r, sum);
+}
+
+// y_0 = r_0 and y_{nb-1} = r_{nb-1}, the first vectors of the two chains, for every system (blockIdx.y: the end, z: the system)
+__global__ void k_pc_copy_ends(int m, int nb, size_t v_tr_stride, const double* __restrict__ r, double* __restrict__ y) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const size_t at = (size_t)blockIdx.z * v_tr_stride + (size_t)(blockIdx.y ? nb - 1 : 0) * m + i;
+    y[at] = r[at];
 }
 
 __global__ void k_pc_to_f32(const double* __restrict__ src, float* __restrict__ dst, size_t n) {
@@ -866,8 +1079,13 @@ int precond_build(nk2d_ctx* c, int mode, int nt, int nslot, int nsys, const doub
     // phosphorus preconditioner factorises three shifted systems per Newton iteration)
     // (option "pc_fp32": single precision storage of the explicit inverses, for the shifted systems of mode 1 too)
     const int want32 = c->pc_fp32 ? 1 : 0;
+    // (option "pc_two_ended": read here, at every set-up; the work buffers of a round hold both chains, so a change of the
+    // value is a new allocation)
+    const int want_ends = c->pc_two_ended ? 1 : 0;
+    if (want_ends && c->pc_valu)
+        return nk2d_fail(c, "preconditioner set-up: pc_two_ended 1 has no round-1 kernels (pc_valu 1); set one of the two to 0");
     const bool reuse = pc && pc->mode == mode && pc->nt == nt && pc->m == m && pc->nb == c->ny && pc->cap_sys >= nsys &&
-                       pc->fp32 == want32;
+                       pc->fp32 == want32 && pc->two_ended == want_ends;
     if (!reuse) {
         nk2d_precond_free(c);
         pc = new Precond();
@@ -875,6 +1093,7 @@ int precond_build(nk2d_ctx* c, int mode, int nt, int nslot, int nsys, const doub
         pc->PJ = pc->SINV = pc->BUF = pc->YV = pc->XV = pc->ROWS = pc->PREV = pc->RV = pc->X0 = pc->PINV = nullptr;
         pc->SINV32 = nullptr;
         pc->fp32 = want32;
+        pc->two_ended = want_ends;
         pc->cap_sys = std::max(nsys, mode == 1 ? 2 : nsys);
     }
     pc->mode = mode;
@@ -884,24 +1103,26 @@ int precond_build(nk2d_ctx* c, int mode, int nt, int nslot, int nsys, const doub
     pc->tc = c->tc;
     pc->m = m;
     pc->nb = c->ny;
+    pc->jm = pc->nb / 2;
     pc->dt = (c->d.t1 - c->d.t0) / 3;
     pc->scale = 0.0;
     for (int i = 0; i < NK2D_MAX_SHIFTS; ++i) pc->sigma[i] = 0.0;
     const size_t P = (size_t)c->nz * c->ny, mm = (size_t)pc->m * pc->m;
     if (!reuse) {
         const size_t cap = (size_t)pc->cap_sys;
+        const size_t gj = pc->two_ended ? 2 * cap : cap;   // systems of one Gauss-Jordan round
         NK2D_CHECK(c, hipMalloc((void**)&pc->PJ, sizeof(double) * pc->nt * PL_COUNT * P));
         if (pc->fp32) {
             NK2D_CHECK(c, hipMalloc((void**)&pc->SINV32, sizeof(float) * cap * pc->nb * mm));
-            NK2D_CHECK(c, hipMalloc((void**)&pc->PREV, sizeof(double) * cap * mm));
+            NK2D_CHECK(c, hipMalloc((void**)&pc->PREV, sizeof(double) * gj * mm));
             NK2D_CHECK(c, hipMalloc((void**)&pc->RV, sizeof(double) * cap * pc->nb * pc->m));
             NK2D_CHECK(c, hipMalloc((void**)&pc->X0, sizeof(double) * cap * pc->nb * pc->m));
         } else {
             NK2D_CHECK(c, hipMalloc((void**)&pc->SINV, sizeof(double) * cap * pc->nb * mm));
         }
-        NK2D_CHECK(c, hipMalloc((void**)&pc->BUF, sizeof(double) * 2 * cap * mm));
-        NK2D_CHECK(c, hipMalloc((void**)&pc->PINV, sizeof(double) * 2 * cap * PC_NB * PC_NB));
-        NK2D_CHECK(c, hipMalloc((void**)&pc->ROWS, sizeof(double) * cap * PC_NB * pc->m));
+        NK2D_CHECK(c, hipMalloc((void**)&pc->BUF, sizeof(double) * 2 * gj * mm));
+        NK2D_CHECK(c, hipMalloc((void**)&pc->PINV, sizeof(double) * 2 * gj * PC_NB * PC_NB));
+        NK2D_CHECK(c, hipMalloc((void**)&pc->ROWS, sizeof(double) * gj * PC_NB * pc->m));
         NK2D_CHECK(c, hipMalloc((void**)&pc->YV, sizeof(double) * cap * pc->nb * pc->m));
         NK2D_CHECK(c, hipMalloc((void**)&pc->XV, sizeof(double) * cap * pc->nb * pc->m));
     }
@@ -917,59 +1138,115 @@ int precond_build(nk2d_ctx* c, int mode, int nt, int nslot, int nsys, const doub
     return 0;
 }
 
+// the Gauss-Jordan panel steps on the `nsys` matrices in the first half of BUF; returns the half the inverses are in
+int pc_gj_invert(nk2d_ctx* c, Precond* pc, int nsys) {
+    const size_t mm = (size_t)pc->m * pc->m;
+    const int m = pc->m;
+    int src = 0;
+    for (int p0 = 0; p0 < m; p0 += PC_NB) {
+        const int nbk = std::min(PC_NB, m - p0);
+        const double* from = pc->BUF + (size_t)src * nsys * mm;
+        double* to = pc->BUF + (size_t)(1 - src) * nsys * mm;
+        // (measured, set-up of iage: 416 x 416 0.529 -> 0.496 s, 208 x 208 0.088 -> 0.096 s, 104 x 104 0.022 -> 0.024 s --
+        // the launch is as long as its one workgroup that also inverts the next pivot block, 13 of ~ 22 us at every size;
+        // value 1 therefore takes it from m = 1024, 2 everywhere: profiles/r04_pc_fused_panel_step.log)
+        if (!c->pc_valu && (c->pc_fused >= 2 || (c->pc_fused == 1 && m >= 1024))) {
+            // (the first pivot block's inverse by a launch of its own, the others by the step before)
+            double* pin = pc->PINV + (size_t)((p0 / PC_NB) & 1) * nsys * PC_NB * PC_NB;
+            double* pout = pc->PINV + (size_t)(1 - ((p0 / PC_NB) & 1)) * nsys * PC_NB * PC_NB;
+            if (p0 == 0)
+                hipLaunchKernelGGL(k_pc_pivot_invert, dim3(1, 1, nsys), dim3(256), 0, nk2d_s(c), m, 0, nbk, from, pin);
+            hipLaunchKernelGGL(k_pc_gj_step, dim3((m + 63) / 64, (m + 63) / 64, nsys), dim3(256), 0, nk2d_s(c), m, p0, nbk, from, to,
+                               (const double*)pin, pout);
+            src = 1 - src;
+            continue;
+        }
+        hipLaunchKernelGGL(k_pc_gj_rows, dim3((m + 255) / 256, nbk, nsys), dim3(256), 0, nk2d_s(c), m, p0, nbk, from,
+                           pc->ROWS);
+        if (c->pc_valu)
+            hipLaunchKernelGGL(k_pc_gj_update, dim3((m + 63) / 64, (m + 63) / 64, nsys), dim3(256), 0, nk2d_s(c), m, p0,
+                               nbk, from, pc->ROWS, to);
+        else
+            hipLaunchKernelGGL(k_pc_gj_update_mfma, dim3((m + 63) / 64, (m + 63) / 64, nsys), dim3(256), 0, nk2d_s(c),
+                               m, p0, nbk, from, pc->ROWS, to);
+        src = 1 - src;
+    }
+    return src;
+}
+
+// the inverse `inv` of the block of column j of system sys into its slot of SINV / SINV32; single precision storage keeps
+// it once more in double precision, in slot `prev` of PREV, for the next column of its chain
+int pc_store_inverse(nk2d_ctx* c, Precond* pc, const double* inv, int sys, int j, int prev) {
+    const size_t mm = (size_t)pc->m * pc->m;
+    if (pc->fp32) {
+        hipLaunchKernelGGL(k_pc_to_f32, dim3((unsigned)((mm + 255) / 256)), dim3(256), 0, nk2d_s(c), inv,
+                           pc->SINV32 + ((size_t)sys * pc->nb + j) * mm, mm);
+        NK2D_CHECK(c, hipMemcpyAsync(pc->PREV + (size_t)prev * mm, inv, sizeof(double) * mm, hipMemcpyDeviceToDevice, nk2d_s(c)));
+    } else {
+        NK2D_CHECK(c, hipMemcpyAsync(pc->SINV + ((size_t)sys * pc->nb + j) * mm, inv, sizeof(double) * mm,
+                                     hipMemcpyDeviceToDevice, nk2d_s(c)));
+    }
+    return 0;
+}
+
+// Elimination from both ends of the ypos axis at once (option "pc_two_ended", a twisted factorisation): the left chain
+// S_0 .. S_{jm-1} is the one-ended elimination, the right chain T_{nb-1} .. T_{jm+1} its mirror image, and round s inverts
+// S_s and T_{nb-1-s} in the SAME launches (2 nsys systems in the grid's z); the chains meet in Z of column jm = nb / 2.
+// jm + 1 dependent rounds instead of nb.  The left chain is the longer one when nb is even: its last round runs alone.
+int precond_eliminate_ends(nk2d_ctx* c) {
+    Precond* pc = (Precond*)c->precond;
+    const int nsys = pc->nsys, m = pc->m, nb = pc->nb, jm = pc->jm;
+    const size_t mm = (size_t)m * m;
+    PcDev D = make_pcdev(c, pc);
+    const dim3 blk(256);
+    // the inverse the block of column j is corrected with: inside SINV, or -- single precision storage -- the double
+    // precision copies of the two chains' last columns, PREV [2][nsys][m][m]
+    const size_t stride = pc->fp32 ? mm : (size_t)nb * mm;
+    auto below = [&](int j) -> const double* { return (j <= 0) ? nullptr : pc->fp32 ? pc->PREV : pc->SINV + (size_t)(j - 1) * mm; };
+    auto above = [&](int j) -> const double* {
+        return (j >= nb - 1) ? nullptr : pc->fp32 ? pc->PREV + (size_t)nsys * mm : pc->SINV + (size_t)(j + 1) * mm;
+    };
+    c->pc_setup_rounds = 0;
+    for (int s = 0; s <= jm; ++s) {
+        const int jl = s, jr = nb - 1 - s;
+        const bool meet = s == jm, pair = !meet && jr > jm;
+        const int nz_ = pair ? 2 * nsys : nsys;
+        const PcSchurEnd e0 = {jl, below(jl), meet ? above(jl) : nullptr};
+        const PcSchurEnd e1 = {jr, nullptr, above(jr)};
+        hipLaunchKernelGGL(k_pc_schur_ends, dim3((m + 255) / 256, m, nz_), blk, 0, nk2d_s(c), D, nsys, e0, e1, stride, pc->BUF);
+        const int src = pc_gj_invert(c, pc, nz_);
+        for (int z = 0; z < nz_; ++z) {
+            const int sys = z % nsys;
+            NK2D_TRY(pc_store_inverse(c, pc, pc->BUF + ((size_t)src * nz_ + z) * mm, sys, z < nsys ? jl : jr, z));
+        }
+        NK2D_CHECK(c, hipGetLastError());
+        c->pc_setup_rounds += 1;
+        // bounded queue depth, as in the one-ended elimination
+        if ((s & 3) == 3) NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+    }
+    NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+    return 0;
+}
+
 int precond_eliminate(nk2d_ctx* c) {
     Precond* pc = (Precond*)c->precond;
+    if (pc->two_ended) return precond_eliminate_ends(c);
     const int nsys = pc->nsys;
     const size_t mm = (size_t)pc->m * pc->m;
     PcDev D = make_pcdev(c, pc);
     const int m = pc->m;
     const dim3 blk(256), grd((m + 255) / 256, m, nsys);
+    c->pc_setup_rounds = 0;
     for (int j = 0; j < pc->nb; ++j) {
         // the Schur inverse of the column before: inside SINV ([nsys][nb][m][m]), or -- single precision storage -- the
         // double precision copy kept of that one column ([nsys][m][m])
         const double* prev = (j > 0) ? (pc->fp32 ? pc->PREV : pc->SINV + (size_t)(j - 1) * mm) : nullptr;
         hipLaunchKernelGGL(k_pc_schur, grd, blk, 0, nk2d_s(c), D, j, prev, pc->fp32 ? mm : (size_t)pc->nb * mm, pc->BUF);
-        int src = 0;
-        for (int p0 = 0; p0 < m; p0 += PC_NB) {
-            const int nbk = std::min(PC_NB, m - p0);
-            const double* from = pc->BUF + (size_t)src * nsys * mm;
-            double* to = pc->BUF + (size_t)(1 - src) * nsys * mm;
-            // (measured, set-up of iage: 416 x 416 0.529 -> 0.496 s, 208 x 208 0.088 -> 0.096 s, 104 x 104 0.022 -> 0.024 s --
-            // the launch is as long as its one workgroup that also inverts the next pivot block, 13 of ~ 22 us at every size;
-            // value 1 therefore takes it from m = 1024, 2 everywhere: profiles/r04_pc_fused_panel_step.log)
-            if (!c->pc_valu && (c->pc_fused >= 2 || (c->pc_fused == 1 && m >= 1024))) {
-                // (the first pivot block's inverse by a launch of its own, the others by the step before)
-                double* pin = pc->PINV + (size_t)((p0 / PC_NB) & 1) * nsys * PC_NB * PC_NB;
-                double* pout = pc->PINV + (size_t)(1 - ((p0 / PC_NB) & 1)) * nsys * PC_NB * PC_NB;
-                if (p0 == 0)
-                    hipLaunchKernelGGL(k_pc_pivot_invert, dim3(1, 1, nsys), dim3(256), 0, nk2d_s(c), m, 0, nbk, from, pin);
-                hipLaunchKernelGGL(k_pc_gj_step, dim3((m + 63) / 64, (m + 63) / 64, nsys), dim3(256), 0, nk2d_s(c), m, p0, nbk, from, to,
-                                   (const double*)pin, pout);
-                src = 1 - src;
-                continue;
-            }
-            hipLaunchKernelGGL(k_pc_gj_rows, dim3((m + 255) / 256, nbk, nsys), dim3(256), 0, nk2d_s(c), m, p0, nbk, from,
-                               pc->ROWS);
-            if (c->pc_valu)
-                hipLaunchKernelGGL(k_pc_gj_update, dim3((m + 63) / 64, (m + 63) / 64, nsys), dim3(256), 0, nk2d_s(c), m, p0,
-                                   nbk, from, pc->ROWS, to);
-            else
-                hipLaunchKernelGGL(k_pc_gj_update_mfma, dim3((m + 63) / 64, (m + 63) / 64, nsys), dim3(256), 0, nk2d_s(c),
-                                   m, p0, nbk, from, pc->ROWS, to);
-            src = 1 - src;
-        }
-        for (int sys = 0; sys < nsys; ++sys) {
-            const double* inv = pc->BUF + ((size_t)src * nsys + sys) * mm;
-            if (pc->fp32) {
-                hipLaunchKernelGGL(k_pc_to_f32, dim3((unsigned)((mm + 255) / 256)), dim3(256), 0, nk2d_s(c), inv,
-                                   pc->SINV32 + ((size_t)sys * pc->nb + j) * mm, mm);
-                NK2D_CHECK(c, hipMemcpyAsync(pc->PREV + (size_t)sys * mm, inv, sizeof(double) * mm, hipMemcpyDeviceToDevice, nk2d_s(c)));
-            } else {
-                NK2D_CHECK(c, hipMemcpyAsync(pc->SINV + ((size_t)sys * pc->nb + j) * mm, inv, sizeof(double) * mm,
-                                             hipMemcpyDeviceToDevice, nk2d_s(c)));
-            }
-        }
+        const int src = pc_gj_invert(c, pc, nsys);
+        for (int sys = 0; sys < nsys; ++sys)
+            NK2D_TRY(pc_store_inverse(c, pc, pc->BUF + ((size_t)src * nsys + sys) * mm, sys, j, sys));
         NK2D_CHECK(c, hipGetLastError());
+        c->pc_setup_rounds += 1;
         // bounded queue depth: a column is ~80 launches, and the whole elimination used to be queued (33 000
         // launches at 416 x 416) before the first synchronisation.  Under `rocprofv3 --pmc` that crashed the
         // profiler's dispatch interceptor (SIGSEGV in librocprofiler-sdk.so reached from this loop's
@@ -981,10 +1258,79 @@ int precond_eliminate(nk2d_ctx* c) {
     return 0;
 }
 
+// Substitution from both ends (option "pc_two_ended"): both chains advance by a column per launch, inward to the block
+// they meet in, then outward from it: at most nb + 1 dependent mat-vec launches instead of 2 nb - 1
+int precond_substitute_ends(nk2d_ctx* c, int sys0, int nsys) {
+    Precond* pc = (Precond*)c->precond;
+    PcDev D = make_pcdev(c, pc);
+    const int m = pc->m, nb = pc->nb, jm = pc->jm;
+    const size_t mm = (size_t)m * m;
+    const size_t mstride = (size_t)nb * mm;      // system stride inside SINV
+    const size_t vstride = (size_t)nb * m;       // system stride inside YV / XV
+    const double* sinv = pc->fp32 ? nullptr : pc->SINV + (size_t)sys0 * mstride;
+    const float* sinv32 = pc->fp32 ? pc->SINV32 + (size_t)sys0 * mstride : nullptr;
+    double* yv = pc->YV + (size_t)sys0 * vstride;
+    double* xv = pc->XV + (size_t)sys0 * vstride;
+    const bool wide = (m % 2 == 0) && m <= PC_GEMV_XMAX;
+    int launches = 0;
+    // one or two chains' steps as one launch
+    auto launch = [&](int mode, int n, const PcEnd& e0, const PcEnd& e1) {
+        const dim3 blk(256), grd((m + 3) / 4, nsys, n);
+        if (pc->fp32)
+            hipLaunchKernelGGL(k_pc_gemv32_ends, grd, blk, 0, nk2d_s(c), D, mode, e0, e1, sinv32, mstride, vstride);
+        else if (wide)
+            hipLaunchKernelGGL(k_pc_gemv2_ends, grd, blk, 0, nk2d_s(c), D, mode, e0, e1, sinv, mstride, vstride);
+        else
+            hipLaunchKernelGGL(k_pc_gemv_ends, grd, blk, 0, nk2d_s(c), D, mode, e0, e1, sinv, mstride, vstride);
+        ++launches;
+    };
+    auto y = [&](int j) { return yv + (size_t)j * m; };
+    auto x = [&](int j) { return xv + (size_t)j * m; };
+    hipLaunchKernelGGL(k_pc_copy_ends, dim3((m + 255) / 256, nb > 1 ? 2 : 1, nsys), dim3(256), 0, nk2d_s(c), m, nb, vstride,
+                       (const double*)xv, yv);
+    // inward: y_j = r_j - l_j o (S_{j-1}^-1 y_{j-1}) for j = 1 .. jm - 1, y_j = r_j - u_j o (T_{j+1}^-1 y_{j+1}) for
+    // j = nb - 2 .. jm; the right chain ends in the meeting block
+    for (int t = 1;; ++t) {
+        const int jl = t, jr = nb - 1 - t;
+        const bool has_l = jl <= jm - 1, has_r = jr >= jm;
+        if (!has_l && !has_r) break;
+        const PcEnd el = {jl, 0, (size_t)(jl - 1) * mm, has_l ? y(jl - 1) : nullptr, has_l ? x(jl) : nullptr, has_l ? y(jl) : nullptr, nullptr, nullptr};
+        const PcEnd er = {jr, 1, (size_t)(jr + 1) * mm, has_r ? y(jr + 1) : nullptr, has_r ? x(jr) : nullptr, has_r ? y(jr) : nullptr, nullptr, nullptr};
+        if (has_l && has_r) launch(0, 2, el, er);
+        else if (has_l) launch(0, 1, el, el);
+        else launch(0, 1, er, er);
+    }
+    // ... then the left chain's correction of the meeting block, on top of the right chain's (or of r_jm = y_{nb-1})
+    if (jm >= 1) {
+        const PcEnd el = {jm, 0, (size_t)(jm - 1) * mm, y(jm - 1), y(jm), y(jm), nullptr, nullptr};
+        launch(0, 1, el, el);
+    }
+    // outward: x_jm = Z^-1 y_jm, then x_j = S_j^-1 (y_j - u_j o x_{j+1}) and x_j = T_j^-1 (y_j - l_j o x_{j-1}); every
+    // launch leaves the corrected y behind for the next one on its side(s)
+    {
+        const PcEnd e = {jm, 0, (size_t)jm * mm, y(jm), nullptr, x(jm), jm > 0 ? y(jm - 1) : nullptr, jm < nb - 1 ? y(jm + 1) : nullptr};
+        launch(1, 1, e, e);
+    }
+    for (int d = 1;; ++d) {
+        const int jl = jm - d, jr = jm + d;
+        const bool has_l = jl >= 0, has_r = jr <= nb - 1;
+        if (!has_l && !has_r) break;
+        const PcEnd el = {jl, 0, has_l ? (size_t)jl * mm : 0, has_l ? y(jl) : nullptr, nullptr, has_l ? x(jl) : nullptr, jl > 0 ? y(jl - 1) : nullptr, nullptr};
+        const PcEnd er = {jr, 1, has_r ? (size_t)jr * mm : 0, has_r ? y(jr) : nullptr, nullptr, has_r ? x(jr) : nullptr, nullptr, (has_r && jr < nb - 1) ? y(jr + 1) : nullptr};
+        if (has_l && has_r) launch(1, 2, el, er);
+        else if (has_l) launch(1, 1, el, el);
+        else launch(1, 1, er, er);
+    }
+    NK2D_CHECK(c, hipGetLastError());
+    c->pc_sub_launches = launches;
+    return 0;
+}
+
 // block forward / backward substitution of systems [sys0, sys0 + nsys) with the right-hand
 // sides already in XV; the solutions end up in XV
 int precond_substitute(nk2d_ctx* c, int sys0, int nsys) {
     Precond* pc = (Precond*)c->precond;
+    if (pc->two_ended) return precond_substitute_ends(c, sys0, nsys);   // (as it was factorised, not the current option)
     PcDev D = make_pcdev(c, pc);
     const int m = pc->m, nb = pc->nb;
     const size_t mm = (size_t)m * m;
@@ -1031,6 +1377,7 @@ int precond_substitute(nk2d_ctx* c, int sys0, int nsys) {
                                (j > 0) ? yv + (size_t)(j - 1) * m : (double*)nullptr);
     }
     NK2D_CHECK(c, hipGetLastError());
+    c->pc_sub_launches = 2 * (int64_t)nb - 1;
     return 0;
 }
 

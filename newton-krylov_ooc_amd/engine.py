@@ -212,6 +212,9 @@ class ModuleEngine:
             self.set_option("stream_hist", float(os.environ["NK2D_STREAM_HIST"]))
         if "NK2D_STREAM_HIST_MB" in os.environ:
             self.set_option("stream_hist_mb", float(os.environ["NK2D_STREAM_HIST_MB"]))
+        # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
+        if "NK2D_PC_TWO_ENDED" in os.environ:
+            self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
         self.set_option("jac_fresh", float(os.environ.get("NK2D_JAC_FRESH", DEFAULT_JAC_FRESH)))
         self.set_option("growth_cap", float(os.environ.get("NK2D_GROWTH_CAP", DEFAULT_GROWTH_CAP)))
         self.set_option("jac_stage", float(os.environ.get("NK2D_JAC_STAGE", DEFAULT_JAC_STAGE)))
