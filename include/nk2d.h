@@ -220,10 +220,18 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    per schedule at 416 x 416, where the year takes 115 - 120 ms instead of 190 ms; "frozen_cache_after": frozen years of a schedule
    that run launch by launch before its cache is built, default 0; "frozen_alloc_async" 1, default: a cache above 8 GB is
    allocated by a thread of the library's own -- hipMalloc of 120 GB takes 0.03 to 3 s -- and the years of the meantime run
-   launch by launch).  Same device functions, bit-identical results; a year that does not pass the Newton check, or a
+   launch by launch; "frozen_cache_pieces" 0, default, or 1, opt-in: the cache is a list of equally sized pieces, one hipMalloc
+   each, instead of one slab -- piece p holds rows [p B, (p + 1) B) laid out as a slab of B rows, B = max(1, floor(
+   "frozen_cache_piece_mb" MiB / bytes of a row)), default 1024 MiB, or "frozen_cache_piece_rows" (default 0: unset) directly; a
+   schedule of n rows needs ceil(n / B) pieces, pieces are kept from schedule to schedule and only added to, the limits above
+   apply to their sum, the thread allocates piece by piece and all its pieces are adopted together, switching the option frees
+   the other form first; "frozen_cache_early" 0, default, or 1, with pieces only: nk2d_comp_fcn with `record` asks the thread for
+   the pieces of the schedule it recorded when the year ends, whatever their size).  Same device functions, bit-identical results; a year that does not pass the Newton check, or a
    barrier that times out, is handed to the launch-per-phase path.  Counters by name: "frozen_persistent_years",
    "frozen_team_years" (of them: a four-wave team per column), "frozen_cache_bytes",
-   "frozen_launch_us" (device time of those launches), "frozen_cache_pending" (1 while a thread allocates a large cache),
+   "frozen_launch_us" (device time of those launches), "frozen_cache_pending" (1 while a thread allocates a large cache or pieces),
+   "frozen_cache_pieces" (pieces held; "frozen_cache_bytes" is then their sum), "frozen_cache_piece_allocs" (pieces allocated
+   so far), "frozen_cache_early_requests" (early requests made),
    "frozen_cache_builds", "frozen_fallbacks", "frozen_resumes"; of the host-side controller: "spec_launches_dropped",
    "spec_front_launches_dropped", "err_estimates_queued", "err_estimates_dropped" (work queued ahead of a verdict); of the
    preconditioner (option "pc_two_ended"): "pc_setup_rounds" (dependent inversion rounds of the last block elimination: ny,

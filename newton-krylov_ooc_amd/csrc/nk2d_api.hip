@@ -214,6 +214,27 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
     if (key == "frozen_alloc_async") { c->frozen_alloc_async = value != 0.0; return 0; }
     if (key == "frozen_persistent_max_e") { c->frozen_persistent_max_e = (int)value; return 0; }
     if (key == "frozen_cache_gb") { c->frozen_cache_max_gb = value; return 0; }
+    if (key == "frozen_cache_pieces") {
+        // the schedule cache as a list of equally sized pieces instead of one slab (nk2d_frozen.hip); taken at the next frozen year
+        if (value != 0.0 && value != 1.0) return nk2d_fail(c, "nk2d_set_option: frozen_cache_pieces is 0 or 1");
+        c->frozen_cache_pieces = (int)value;
+        return 0;
+    }
+    if (key == "frozen_cache_piece_mb") {
+        if (!(value > 0.0) || !std::isfinite(value)) return nk2d_fail(c, "nk2d_set_option: frozen_cache_piece_mb must be > 0");
+        c->frozen_cache_piece_mb = value;
+        return 0;
+    }
+    if (key == "frozen_cache_piece_rows") {
+        if (!(value >= 0.0) || value > 1.0e9) return nk2d_fail(c, "nk2d_set_option: frozen_cache_piece_rows must be 0 (from frozen_cache_piece_mb) or a row count");
+        c->frozen_cache_piece_rows = (int64_t)value;
+        return 0;
+    }
+    if (key == "frozen_cache_early") {
+        if (value != 0.0 && value != 1.0) return nk2d_fail(c, "nk2d_set_option: frozen_cache_early is 0 or 1");
+        c->frozen_cache_early = (int)value;
+        return 0;
+    }
     if (key == "barrier_timeout_ms") {
         if (!(value >= 0.0)) return nk2d_fail(c, "nk2d_set_option: barrier_timeout_ms must be >= 0");
         c->barrier_timeout_ms = value;
@@ -569,6 +590,11 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_cache_builds = c->frozen_persistent_years = 0;
     c->frozen_team = 1;
     c->frozen_cache_after = 0;
+    c->frozen_cache_pieces = 0;
+    c->frozen_cache_piece_mb = 1024.0;
+    c->frozen_cache_piece_rows = 0;
+    c->frozen_cache_early = 0;
+    c->frozen_cache_piece_allocs = c->frozen_cache_early_requests = 0;
     c->frozen_coef_lds = 15;
     c->frozen_by_column = 1;
     c->strm = nullptr;
@@ -1051,7 +1077,11 @@ extern "C" int nk2d_comp_fcn(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, nk2d_stats* s
                              int64_t replay_n, double* record, int64_t record_cap, int64_t* record_n) {
     NK2D_CHECK(c, hipSetDevice(c->dev));
     if (record_n) *record_n = 0;
-    return nk2d_radau_year(c, x, fx, stats, replay, replay_n, record, record_cap, record_n);
+    const int rc = nk2d_radau_year(c, x, fx, stats, replay, replay_n, record, record_cap, record_n);
+    // option "frozen_cache_early" (with "frozen_cache_pieces"): the pieces of the schedule this year recorded are asked for now
+    if (rc == 0 && record && record_n && *record_n > 0 && c->frozen_cache_pieces && c->frozen_cache_early)
+        NK2D_TRY(nk2d_frozen_cache_early(c, record, *record_n));
+    return rc;
 }
 
 // forward year on a schedule this library recorded itself (nk2d_comp_fcn with `record`) under the same options: the
@@ -1106,6 +1136,9 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_launch_us") v = c->frozen_launch_us;
     else if (key == "frozen_cache_pending") v = nk2d_frozen_cache_pending(c);
     else if (key == "frozen_cache_bytes") v = nk2d_frozen_cache_bytes(c);
+    else if (key == "frozen_cache_pieces") v = nk2d_frozen_cache_npieces(c);
+    else if (key == "frozen_cache_piece_allocs") v = nk2d_frozen_cache_piece_allocs(c);
+    else if (key == "frozen_cache_early_requests") v = c->frozen_cache_early_requests;
     else if (key == "frozen_fallbacks") v = c->frozen_fallbacks;
     else if (key == "frozen_resumes") v = c->frozen_resumes;
     else if (key == "spec_launches_dropped") v = c->cnt_spec_dropped;

@@ -2005,6 +2005,49 @@ struct CachePtrs {
     size_t kv_len, np, nv, ntab;
 };
 
+// The same cache as a list of equally sized PIECES (option "frozen_cache_pieces"): piece p holds rows [p rows, (p + 1) rows),
+// laid out inside as a slab with room for `rows` rows -- the eight tables in CachePtrs' order at fixed offsets (in doubles)
+struct PieceTab {
+    double* const* base;                                // [pieces] on the device
+    int rows;                                           // rows per piece
+    size_t oJ, ofr, ofcr, ofci, otr, otcr, otci;        // where J, fr_inv, ... start inside a piece (KV starts it)
+};
+
+// the tables of ONE row
+struct RowTabs {
+    double *KV, *J, *fr_inv, *fc_invr, *fc_invi, *fr_tab, *fc_tabr, *fc_tabi;
+};
+
+// a pointer every lane holds identically, into scalar registers
+__device__ __forceinline__ double* uni_p(double* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return (double*)(((unsigned long long)hi << 32) | lo);
+}
+
+// row r of the piece that starts at `b` (C: the sizes of the tables)
+__device__ __forceinline__ RowTabs piece_row_tabs(const CachePtrs& C, const PieceTab& T, double* b, int r) {
+    RowTabs t;
+    t.KV = b + (size_t)r * 3 * C.kv_len;
+    t.J = b + T.oJ + (size_t)r * 5 * C.np;
+    t.fr_inv = b + T.ofr + (size_t)r * C.nv;
+    t.fc_invr = b + T.ofcr + (size_t)r * C.nv;
+    t.fc_invi = b + T.ofci + (size_t)r * C.nv;
+    t.fr_tab = b + T.otr + (size_t)r * C.ntab;
+    t.fc_tabr = b + T.otcr + (size_t)r * C.ntab;
+    t.fc_tabi = b + T.otci + (size_t)r * C.ntab;
+    return t;
+}
+
+// what the cache kernels take for a cache in pieces: the sizes of CachePtrs (its table pointers unused) and the pieces
+struct CachePiecePtrs {
+    CachePtrs C;
+    PieceTab T;
+};
+template <int PIECES> struct CacheArgOf { typedef CachePtrs type; };
+template <> struct CacheArgOf<1> { typedef CachePiecePtrs type; };
+
 // The single-phase Newton iteration (stage + one sweep + update) of newton_fused_body for the one-launch year of a small
 // grid, with EVERY operand requested before the first is used.  A wave issues in order: in the generic body the Jacobian
 // planes and the factorisation are asked for behind the stage arithmetic, W again behind the solves -- four round trips
@@ -2172,6 +2215,14 @@ struct FrozenArgs {
     int coef_lds;                // option "frozen_coef_lds" (bits of LdsSrc): what a wave finds in LDS; bits 2, 3 need `by_column`
     int by_column;               // 1: a workgroup is ONE ypos column with all its tracers (a wave each) instead of adjacent columns of one tracer
 };
+
+// the arguments of the piece flavour of k_frozen_persistent: those of the slab flavour (the table pointers of C unused, its
+// sizes used) and the pieces.  The slab flavour's argument stays FrozenArgs
+struct FrozenPieceArgs : FrozenArgs {
+    PieceTab T;
+};
+template <int PIECES> struct FrozenArgOf { typedef FrozenArgs type; };
+template <> struct FrozenArgOf<1> { typedef FrozenPieceArgs type; };
 
 // f = fun(t, y) of the column (the plane kvp is the mixing plane at t): the tendency at a step start, for the error estimate
 template <int E, int KIND, int MP>

@@ -140,6 +140,12 @@ struct nk2d_ctx {
     int frozen_by_column; // option "frozen_by_column": a workgroup of the one-launch year is one ypos column with all its tracers
     int frozen_alloc_async;   // option "frozen_alloc_async": a schedule cache above 8 GB is allocated by a thread of its own
     int frozen_cache_after;   // option "frozen_cache_after": frozen years of a schedule that run launch by launch before its cache is built (default 0; -1: 0 for a cache below 8 GB, 3 above)
+    // option "frozen_cache_pieces": the schedule cache as a list of equally sized pieces (one hipMalloc each) instead of one slab
+    int frozen_cache_pieces;          // 0 (default): the slab, 1: pieces
+    double frozen_cache_piece_mb;     // option "frozen_cache_piece_mb": size of a piece in MiB (rows per piece = floor of it over a row's bytes, at least 1)
+    int64_t frozen_cache_piece_rows;  // option "frozen_cache_piece_rows": rows per piece directly (0: from the size in MiB)
+    int frozen_cache_early;           // option "frozen_cache_early": with pieces, the year that records a schedule asks for its pieces when it ends
+    int64_t frozen_cache_piece_allocs, frozen_cache_early_requests;   // counters: pieces allocated so far, early requests made
     uint64_t frozen_seen_key; int frozen_seen_years;   // the schedule last seen by nk2d_frozen_persistent and its years so far
     int64_t frozen_team_years;
     int64_t frozen_launch_us;   // device time of the one-launch frozen years so far (HIP events around the launch)
@@ -635,6 +641,10 @@ double nk2d_fingerprint(const nk2d_ctx* c);
 uint64_t nk2d_frozen_key(const nk2d_ctx* c, const double* sched, int64_t n);   // schedule ^ fingerprint ^ frozen_err_check
 int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vector<char>* err_rows = nullptr);
 int nk2d_frozen_cache_pending(const nk2d_ctx* c);
+int64_t nk2d_frozen_cache_npieces(const nk2d_ctx* c);
+int64_t nk2d_frozen_cache_piece_allocs(const nk2d_ctx* c);
+// option "frozen_cache_early": the pieces of the schedule a free-running year just recorded, asked for from a thread
+int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n);
 int64_t nk2d_frozen_cache_bytes(const nk2d_ctx* c);
 void nk2d_frozen_cache_free(nk2d_ctx* c);
 int nk2d_prof_window_begin(nk2d_ctx* c);

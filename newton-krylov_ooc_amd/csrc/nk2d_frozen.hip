@@ -4,9 +4,16 @@
 #include <algorithm>
 #include <vector>
 
-// planes and Jacobian of every row: task = (row, slot 0..3, ypos column)
-template <int E>
-__global__ void __launch_bounds__(NK2D_BLOCK) k_cache_planes(DevP P, const CacheRow* __restrict__ rows, CachePtrs C, int n) {
+// the tables of row i of a cache in pieces: in the piece that holds the row
+__device__ __forceinline__ RowTabs cache_row_tabs(const CachePiecePtrs& C, int i) {
+    const int p = i / C.T.rows;
+    return piece_row_tabs(C.C, C.T, C.T.base[p], i - p * C.T.rows);
+}
+
+// planes and Jacobian of every row: task = (row, slot 0..3, ypos column).  PIECES: the cache is a list of pieces (the planes'
+// places are absolute addresses in the rows either way; the Jacobian's are resolved per row)
+template <int E, int PIECES = 0>
+__global__ void __launch_bounds__(NK2D_BLOCK) k_cache_planes(DevP P, const CacheRow* __restrict__ rows, typename CacheArgOf<PIECES>::type C, int n) {
     const int lane = threadIdx.x & 63;
     const long long task = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const long long per_row = 4LL * P.ny;
@@ -21,18 +28,21 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_cache_planes(DevP P, const Cache
         double kv[E], up[E], dn[E], so[E], no[E], ce[E];
         vmix_col_regs<E>(P, R.v.bldmin, R.v.y0, R.v.y1, R.v.hw, R.v.frac[3], j, lane, kv);
         jac_cols<E>(P, kv, j, lane, up, dn, so, no, ce);
-        double* J = C.J + (size_t)i * 5 * C.np;
+        size_t np;
+        double* J;
+        if constexpr (PIECES) { np = C.C.np; J = cache_row_tabs(C, i).J; }
+        else { np = C.np; J = C.J + (size_t)i * 5 * C.np; }
         store_col<E>(J, j, lane, up);
-        store_col<E>(J + C.np, j, lane, dn);
-        store_col<E>(J + 2 * C.np, j, lane, so);
-        store_col<E>(J + 3 * C.np, j, lane, no);
-        store_col<E>(J + 4 * C.np, j, lane, ce);
+        store_col<E>(J + np, j, lane, dn);
+        store_col<E>(J + 2 * np, j, lane, so);
+        store_col<E>(J + 3 * np, j, lane, no);
+        store_col<E>(J + 4 * np, j, lane, ce);
     }
 }
 
 // line factorisation of every row: task = (row, (system, tracer), ypos column) -- the work of k_factor per row
-template <int E, int KIND>
-__global__ void __launch_bounds__(NK2D_BLOCK) k_cache_factor(DevP P, const CacheRow* __restrict__ rows, CachePtrs C, int n) {
+template <int E, int KIND, int PIECES = 0>
+__global__ void __launch_bounds__(NK2D_BLOCK) k_cache_factor(DevP P, const CacheRow* __restrict__ rows, typename CacheArgOf<PIECES>::type C, int n) {
     const int lane = threadIdx.x & 63;
     const long long task = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const long long per_row = 2LL * P.ncol;
@@ -40,10 +50,18 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_cache_factor(DevP P, const Cache
     const int i = (int)(task / per_row), rem = (int)(task - (long long)i * per_row);
     const CacheRow& R = rows[i];
     SweepArgs A = {};
-    const double* J = C.J + (size_t)i * 5 * C.np;
-    A.JL = J; A.JU = J + C.np; A.JS = J + 2 * C.np; A.JN = J + 3 * C.np; A.JC = J + 4 * C.np;
-    A.fr_inv = C.fr_inv + (size_t)i * C.nv; A.fc_invr = C.fc_invr + (size_t)i * C.nv; A.fc_invi = C.fc_invi + (size_t)i * C.nv;
-    A.fr_tab = C.fr_tab + (size_t)i * C.ntab; A.fc_tabr = C.fc_tabr + (size_t)i * C.ntab; A.fc_tabi = C.fc_tabi + (size_t)i * C.ntab;
+    if constexpr (PIECES) {
+        const RowTabs t = cache_row_tabs(C, i);
+        const size_t np = C.C.np;
+        A.JL = t.J; A.JU = t.J + np; A.JS = t.J + 2 * np; A.JN = t.J + 3 * np; A.JC = t.J + 4 * np;
+        A.fr_inv = t.fr_inv; A.fc_invr = t.fc_invr; A.fc_invi = t.fc_invi;
+        A.fr_tab = t.fr_tab; A.fc_tabr = t.fc_tabr; A.fc_tabi = t.fc_tabi;
+    } else {
+        const double* J = C.J + (size_t)i * 5 * C.np;
+        A.JL = J; A.JU = J + C.np; A.JS = J + 2 * C.np; A.JN = J + 3 * C.np; A.JC = J + 4 * C.np;
+        A.fr_inv = C.fr_inv + (size_t)i * C.nv; A.fc_invr = C.fc_invr + (size_t)i * C.nv; A.fc_invi = C.fc_invi + (size_t)i * C.nv;
+        A.fr_tab = C.fr_tab + (size_t)i * C.ntab; A.fc_tabr = C.fc_tabr + (size_t)i * C.ntab; A.fc_tabi = C.fc_tabi + (size_t)i * C.ntab;
+    }
     A.f32 = 0;
     A.cre = R.cre; A.ccr = R.ccr; A.cci = R.cci;
     A.nreal = P.ncol; A.ntasks = 2 * P.ncol;
@@ -54,8 +72,11 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_cache_factor(DevP P, const Cache
 // the complex system on the fourth, exchanges through LDS): the phase of a small grid is the dependent arithmetic of one
 // column's Newton iteration, and the team cuts that chain (three tendencies one after the other, then the real and the
 // complex solve one after the other -> one tendency, then both solves side by side).  Same arithmetic, same bits.
-template <int E, int KIND, int TEAM = 0>
-__global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, FrozenArgs A) {
+// PIECES = 1: the cache is a list of pieces (option "frozen_cache_pieces", FrozenPieceArgs): once per row the piece's base comes
+// from the device table by one scalar load and the row's eight table addresses are formed in scalar registers; the phases
+// read them as the slab flavour reads its own.  Everything else is the one body.
+template <int E, int KIND, int TEAM = 0, int PIECES = 0>
+__global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typename FrozenArgOf<PIECES>::type A) {
     constexpr int XCD = 0, NB = 1;      // (rounds 2 - 3 also had all workgroups on one XCD and a grid barrier between the phases)
     __shared__ int lds_ok;
     __shared__ double team_lds[TEAM ? sizeof(TeamLds<E, 3>) / sizeof(double) : 1];
@@ -89,6 +110,8 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, Frozen
     NeighbourSync nbs{(unsigned*)((char*)A.arrive + 8192), A.abort_flag, wg, nb_left, nb_right, 0u, &lds_ok, A.spin_ticks, A.fences};
     const size_t nv = A.C.nv;
     int swapY = 0, swapZ = 0, status = 0, done = 0;
+    int pc_p = 0, pc_r = 0;     // PIECES: row i is row pc_r of piece pc_p (i = pc_p rows + pc_r, kept by counting: no division)
+    (void)pc_p; (void)pc_r;
 #define FZ_Y (swapY ? A.YOLD : A.Y)
 #define FZ_YOLD (swapY ? A.Y : A.YOLD)
 #define FZ_Z (swapZ ? A.ZN : A.Z)
@@ -151,15 +174,31 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, Frozen
         const FrozenRow R = A.rows[i];
         const int n_iter = uni_i(R.n_iter), m = uni_i(R.m);
         const bool last_row = i == A.n - 1;
-        const double* kvb = A.C.KV + (size_t)i * 3 * A.C.kv_len;
-        const double* J = A.C.J + (size_t)i * 5 * A.C.np;
+        // PIECES: the row's tables -- the piece's base (the same for every lane of every wave: one load, the value in scalar
+        // registers) + fixed offsets + r stride; the slab flavour forms base + i stride where it uses them, as it always did
+        RowTabs T = {};
+        const double* kv_prev = nullptr;    // the mixing plane at the step start = the last stage plane of row i - 1
+        (void)T; (void)kv_prev;
+        if constexpr (PIECES) {
+            double* const base = uni_p(A.T.base[pc_p]);
+            T = piece_row_tabs(A.C, A.T, base, pc_r);
+            if (i > 0 && uni_i(R.err) != 0) {
+                // (row i - 1 may be the last row of the piece before: resolved on its own, on the few rows that carry an estimate)
+                const double* pb = pc_r > 0 ? base : uni_p(A.T.base[pc_p - 1]);
+                const int pr = pc_r > 0 ? pc_r - 1 : A.T.rows - 1;
+                kv_prev = pb + ((size_t)pr * 3 + 2) * A.C.kv_len;
+            }
+            if (++pc_r == A.T.rows) { pc_r = 0; ++pc_p; }
+        }
+        const double* kvb = PIECES ? T.KV : A.C.KV + (size_t)i * 3 * A.C.kv_len;
+        const double* J = PIECES ? T.J : A.C.J + (size_t)i * 5 * A.C.np;
         // SciPy's error estimate on this step too (every "frozen_err_check"-th: the host compares it with what the recorded
         // step was accepted with).  Three phases of their own, one wave per column: the tendency at the step start before the
         // Newton iterations, the estimate behind the last of them -- which is then an ordinary iteration --, the end of the step
         const bool with_err = uni_i(R.err) != 0 && !last_row && i > 0;
         if (with_err) {
             if (col_wave && (!TEAM || tw == 0))
-                tend_at_body<E, KIND, MPX>(P, FZ_Y, A.C.KV + ((size_t)(i - 1) * 3 + 2) * A.C.kv_len, A.F, wave, lane);
+                tend_at_body<E, KIND, MPX>(P, FZ_Y, PIECES ? kv_prev : A.C.KV + ((size_t)(i - 1) * 3 + 2) * A.C.kv_len, A.F, wave, lane);
             FZ_SYNC()
         }
         for (int k = 0; k < n_iter; ++k) {
@@ -174,10 +213,15 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, Frozen
                 FA.st.br = A.BR; FA.st.bcr = A.BCR; FA.st.bci = A.BCI;
                 FA.st.nv = nv; FA.st.mreal = R.mreal; FA.st.mcr = R.mcr; FA.st.mci = R.mci;
                 FA.sw.JL = J; FA.sw.JU = J + A.C.np; FA.sw.JS = J + 2 * A.C.np; FA.sw.JN = J + 3 * A.C.np; FA.sw.JC = J + 4 * A.C.np;
-                FA.sw.fr_inv = A.C.fr_inv + (size_t)i * nv; FA.sw.fc_invr = A.C.fc_invr + (size_t)i * nv;
-                FA.sw.fc_invi = A.C.fc_invi + (size_t)i * nv;
-                FA.sw.fr_tab = A.C.fr_tab + (size_t)i * A.C.ntab; FA.sw.fc_tabr = A.C.fc_tabr + (size_t)i * A.C.ntab;
-                FA.sw.fc_tabi = A.C.fc_tabi + (size_t)i * A.C.ntab;
+                if constexpr (PIECES) {
+                    FA.sw.fr_inv = T.fr_inv; FA.sw.fc_invr = T.fc_invr; FA.sw.fc_invi = T.fc_invi;
+                    FA.sw.fr_tab = T.fr_tab; FA.sw.fc_tabr = T.fc_tabr; FA.sw.fc_tabi = T.fc_tabi;
+                } else {
+                    FA.sw.fr_inv = A.C.fr_inv + (size_t)i * nv; FA.sw.fc_invr = A.C.fc_invr + (size_t)i * nv;
+                    FA.sw.fc_invi = A.C.fc_invi + (size_t)i * nv;
+                    FA.sw.fr_tab = A.C.fr_tab + (size_t)i * A.C.ntab; FA.sw.fc_tabr = A.C.fc_tabr + (size_t)i * A.C.ntab;
+                    FA.sw.fc_tabi = A.C.fc_tabi + (size_t)i * A.C.ntab;
+                }
                 FA.sw.f32 = 0;
                 FA.sw.br = A.BR; FA.sw.bcr = A.BCR; FA.sw.bci = A.BCI;
                 FA.sw.xr_old = src ? A.XR[1] : A.XR[0]; FA.sw.xcr_old = src ? A.XCR[1] : A.XCR[0];
@@ -260,8 +304,8 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, Frozen
             if (col_wave && (!TEAM || tw == 0)) {
                 ErrArgs EA = {};
                 EA.sw.JL = J; EA.sw.JU = J + A.C.np; EA.sw.JS = J + 2 * A.C.np; EA.sw.JN = J + 3 * A.C.np; EA.sw.JC = J + 4 * A.C.np;
-                EA.sw.fr_inv = A.C.fr_inv + (size_t)i * nv;
-                EA.sw.fr_tab = A.C.fr_tab + (size_t)i * A.C.ntab;
+                EA.sw.fr_inv = PIECES ? T.fr_inv : A.C.fr_inv + (size_t)i * nv;
+                EA.sw.fr_tab = PIECES ? T.fr_tab : A.C.fr_tab + (size_t)i * A.C.ntab;
                 EA.sw.xr_old = A.XR[0]; EA.sw.xr_new = A.XR[1];
                 EA.f = A.F; EA.z = FZ_Z; EA.y = FZ_Y; EA.nv = nv; EA.h = R.h;
                 EA.part = A.STEP_PART + (size_t)(3 * i + 2) * P.ncol;
@@ -336,7 +380,55 @@ struct nk2d_frozen_cache {
     CacheRow* alloc_rows = nullptr;
     FrozenRow* alloc_frows = nullptr;
     size_t alloc_cap = 0;
+    // option "frozen_cache_pieces": the cache as a list of equally sized pieces instead of the slab -- never both.  Piece p
+    // holds rows [p piece_rows, (p + 1) piece_rows), laid out inside as a slab of that many rows; pieces are kept from
+    // schedule to schedule and only added to
+    std::vector<double*> pieces;
+    size_t piece_rows = 0;
+    double** pieces_dev = nullptr;      // their bases on the device, [pieces_dev_cap]
+    size_t pieces_dev_cap = 0;
+    size_t rows_cap = 0;                // room of rows_dev / frows_dev in this form (they grow on their own)
+    std::vector<double*> alloc_pieces;  // what the thread allocated (valid with alloc_state 2 and alloc_is_pieces)
+    size_t alloc_piece_rows = 0;
+    bool alloc_is_pieces = false;
 };
+
+// doubles of a row of the cache
+static size_t frozen_row_doubles(const nk2d_ctx* c) {
+    const size_t ntab = (size_t)c->ncol * NK2D_TAB * 64;
+    return 3 * c->kv_len + 5 * c->np + 3 * c->nv + 3 * ntab;
+}
+
+// rows per piece: option "frozen_cache_piece_rows", or what fits "frozen_cache_piece_mb" MiB (at least one)
+static size_t frozen_piece_rows(const nk2d_ctx* c) {
+    if (c->frozen_cache_piece_rows > 0) return (size_t)c->frozen_cache_piece_rows;
+    const double fit = std::floor(c->frozen_cache_piece_mb * 1048576.0 / (8.0 * (double)frozen_row_doubles(c)));
+    return fit >= 1.0 ? (size_t)std::min(fit, 1.0e9) : (size_t)1;
+}
+
+static void frozen_free_slab(nk2d_frozen_cache* fc) {
+    if (fc->slab) (void)hipFree(fc->slab);
+    if (fc->rows_dev) (void)hipFree(fc->rows_dev);
+    if (fc->frows_dev) (void)hipFree(fc->frows_dev);
+    fc->slab = nullptr; fc->rows_dev = nullptr; fc->frows_dev = nullptr; fc->cap_rows = 0;
+    fc->C.KV = nullptr;
+    fc->key = 0; fc->n = 0;
+}
+
+static void frozen_free_pieces(nk2d_frozen_cache* fc) {
+    for (double* p : fc->pieces)
+        if (p) (void)hipFree(p);
+    fc->pieces.clear();
+    fc->piece_rows = 0;
+    if (fc->pieces_dev) (void)hipFree(fc->pieces_dev);
+    fc->pieces_dev = nullptr; fc->pieces_dev_cap = 0;
+    if (fc->rows_cap) {
+        if (fc->rows_dev) (void)hipFree(fc->rows_dev);
+        if (fc->frows_dev) (void)hipFree(fc->frows_dev);
+        fc->rows_dev = nullptr; fc->frows_dev = nullptr; fc->rows_cap = 0;
+    }
+    fc->key = 0; fc->n = 0;
+}
 
 static uint64_t sched_key(const double* sched, int64_t n) {
     uint64_t h = 14695981039346656037ull;
@@ -352,7 +444,23 @@ uint64_t nk2d_frozen_key(const nk2d_ctx* c, const double* sched, int64_t n) {
     return sched_key(sched, n) ^ (uint64_t)nk2d_fingerprint(c) ^ ((uint64_t)(c->frozen_err_check + 1) * 0x9E3779B97F4A7C15ull);
 }
 
-// 1 while a thread is allocating the slab of this context's schedule cache
+// where the tables lie inside a piece: the slab's order, with room for piece_rows rows
+static PieceTab frozen_piece_tab(const nk2d_ctx* c, const nk2d_frozen_cache* fc) {
+    const size_t ntab = (size_t)c->ncol * NK2D_TAB * 64, B = fc->piece_rows;
+    PieceTab T;
+    T.base = fc->pieces_dev;
+    T.rows = (int)B;
+    T.oJ = B * 3 * c->kv_len;
+    T.ofr = T.oJ + B * 5 * c->np;
+    T.ofcr = T.ofr + B * c->nv;
+    T.ofci = T.ofcr + B * c->nv;
+    T.otr = T.ofci + B * c->nv;
+    T.otcr = T.otr + B * ntab;
+    T.otci = T.otcr + B * ntab;
+    return T;
+}
+
+// 1 while a thread is allocating the slab (or pieces) of this context's schedule cache
 int nk2d_frozen_cache_pending(const nk2d_ctx* c) {
     const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
     return (fc && fc->alloc_state.load() == 1) ? 1 : 0;
@@ -361,9 +469,25 @@ int nk2d_frozen_cache_pending(const nk2d_ctx* c) {
 // bytes of HBM the schedule cache of this context holds right now
 int64_t nk2d_frozen_cache_bytes(const nk2d_ctx* c) {
     const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
-    if (!fc || !fc->slab) return 0;
+    if (!fc) return 0;
+    if (!fc->pieces.empty()) return (int64_t)(8 * fc->pieces.size() * fc->piece_rows * frozen_row_doubles(c));
+    if (!fc->slab) return 0;
     const size_t ntab = (size_t)c->ncol * NK2D_TAB * 64;
     return (int64_t)(8 * fc->cap_rows * (3 * c->kv_len + 5 * c->np + 3 * c->nv + 3 * ntab));
+}
+
+// pieces allocated for this context so far: those booked, and those a thread has finished allocating and the owner has not
+// adopted yet (an allocation counts when it is made, not when the year that uses it comes)
+int64_t nk2d_frozen_cache_piece_allocs(const nk2d_ctx* c) {
+    const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
+    const bool waiting = fc && fc->alloc_state.load() == 2 && fc->alloc_is_pieces;
+    return c->frozen_cache_piece_allocs + (waiting ? (int64_t)fc->alloc_pieces.size() : 0);
+}
+
+// pieces the schedule cache of this context holds right now (option "frozen_cache_pieces")
+int64_t nk2d_frozen_cache_npieces(const nk2d_ctx* c) {
+    const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
+    return fc ? (int64_t)fc->pieces.size() : 0;
 }
 
 void nk2d_frozen_cache_free(nk2d_ctx* c) {
@@ -374,10 +498,10 @@ void nk2d_frozen_cache_free(nk2d_ctx* c) {
         if (fc->alloc_slab) (void)hipFree(fc->alloc_slab);
         if (fc->alloc_rows) (void)hipFree(fc->alloc_rows);
         if (fc->alloc_frows) (void)hipFree(fc->alloc_frows);
+        for (double* p : fc->alloc_pieces) (void)hipFree(p);
     }
-    if (fc->slab) (void)hipFree(fc->slab);
-    if (fc->rows_dev) (void)hipFree(fc->rows_dev);
-    if (fc->frows_dev) (void)hipFree(fc->frows_dev);
+    frozen_free_pieces(fc);
+    frozen_free_slab(fc);
     delete fc;
     c->frozen_cache = nullptr;
 }
@@ -400,8 +524,8 @@ static size_t frozen_lds_doubles(int E, int bits, bool by_column, int nwaves) {
     return NK2D_COEF_LDS_DOUBLES(E) + ((bits & 4) ? 5 * E * 64 : 0) + (size_t)nwaves * (((bits & 2) ? 3 * E * 64 : 0) + ((bits & 8) ? E * 64 : 0));
 }
 
-template <class K>
-static hipError_t launch_resident(nk2d_ctx* c, K kernel, dim3 grid, dim3 block, DevP& P, FrozenArgs& A, size_t lds_bytes = 0) {
+template <class K, class ARGS>
+static hipError_t launch_resident(nk2d_ctx* c, K kernel, dim3 grid, dim3 block, DevP& P, ARGS& A, size_t lds_bytes = 0) {
     int per_cu = 0;
     hipError_t rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)block.x, lds_bytes);
     if (rc != hipSuccess) return rc;
@@ -418,40 +542,41 @@ static hipError_t launch_resident(nk2d_ctx* c, K kernel, dim3 grid, dim3 block, 
     return hipGetLastError();
 }
 
-template <int E, int KIND, int TEAM>
-static hipError_t launch_frozen_one(nk2d_ctx* c, dim3 grid, DevP& P, FrozenArgs& A) {
+template <int E, int KIND, int TEAM, int PIECES>
+static hipError_t launch_frozen_one(nk2d_ctx* c, dim3 grid, DevP& P, typename FrozenArgOf<PIECES>::type& A) {
     // a team per column: the workgroup IS the column.  A wave per column: option "frozen_wpb" adjacent columns of one tracer to
     // a workgroup (its waves move in lock step, its neighbours are the workgroups to the left and right), or -- by_column --
     // one ypos column with all its tracers.  Three and more levels per lane: a wave's own data of the year in LDS
     const int wpb = TEAM ? NK2D_WAVES_PER_BLOCK : std::max(1, std::min(NK2D_WAVES_PER_BLOCK, c->frozen_wpb));
     const dim3 g = TEAM ? grid : dim3((unsigned)((c->ncol + wpb - 1) / wpb));
     if (!TEAM && E >= 3 && A.by_column)
-        return launch_resident(c, k_frozen_persistent<E, KIND, TEAM>, dim3((unsigned)c->ny), dim3(64 * c->tc), P, A,
+        return launch_resident(c, k_frozen_persistent<E, KIND, TEAM, PIECES>, dim3((unsigned)c->ny), dim3(64 * c->tc), P, A,
                                sizeof(double) * frozen_lds_doubles(E, A.coef_lds, true, c->tc));
     const size_t lds = (!TEAM && E >= 3 && A.coef_lds) ? sizeof(double) * frozen_lds_doubles(E, A.coef_lds, false, wpb) : 0;
-    return launch_resident(c, k_frozen_persistent<E, KIND, TEAM>, g, dim3(64 * wpb), P, A, lds);
+    return launch_resident(c, k_frozen_persistent<E, KIND, TEAM, PIECES>, g, dim3(64 * wpb), P, A, lds);
 }
-template <int KIND, int TEAM>
-static hipError_t launch_frozen_e(nk2d_ctx* c, dim3 grid, DevP& P, FrozenArgs& A) {
+template <int KIND, int TEAM, int PIECES>
+static hipError_t launch_frozen_e(nk2d_ctx* c, dim3 grid, DevP& P, typename FrozenArgOf<PIECES>::type& A) {
     switch (c->E) {
-        case 1: return launch_frozen_one<1, KIND, TEAM>(c, grid, P, A);
-        case 2: return launch_frozen_one<2, KIND, TEAM>(c, grid, P, A);
+        case 1: return launch_frozen_one<1, KIND, TEAM, PIECES>(c, grid, P, A);
+        case 2: return launch_frozen_one<2, KIND, TEAM, PIECES>(c, grid, P, A);
         // three and four levels per lane: a wave per column (all module kinds)
-        case 3: if constexpr (!TEAM) return launch_frozen_one<3, KIND, 0>(c, grid, P, A); else break;
-        case 4: if constexpr (!TEAM) return launch_frozen_one<4, KIND, 0>(c, grid, P, A); else break;
+        case 3: if constexpr (!TEAM) return launch_frozen_one<3, KIND, 0, PIECES>(c, grid, P, A); else break;
+        case 4: if constexpr (!TEAM) return launch_frozen_one<4, KIND, 0, PIECES>(c, grid, P, A); else break;
         // five to eight levels per lane (up to 512 levels): a wave per column, linear sources
-        case 5: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<5, 0, 0>(c, grid, P, A); else break;
-        case 6: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<6, 0, 0>(c, grid, P, A); else break;
-        case 7: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<7, 0, 0>(c, grid, P, A); else break;
-        case 8: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<8, 0, 0>(c, grid, P, A); else break;
+        case 5: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<5, 0, 0, PIECES>(c, grid, P, A); else break;
+        case 6: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<6, 0, 0, PIECES>(c, grid, P, A); else break;
+        case 7: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<7, 0, 0, PIECES>(c, grid, P, A); else break;
+        case 8: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<8, 0, 0, PIECES>(c, grid, P, A); else break;
         default: break;
     }
     return hipErrorInvalidValue;
 }
-static hipError_t launch_frozen(nk2d_ctx* c, bool team, dim3 grid, DevP& P, FrozenArgs& A) {
+template <int PIECES>
+static hipError_t launch_frozen(nk2d_ctx* c, bool team, dim3 grid, DevP& P, typename FrozenArgOf<PIECES>::type& A) {
     const bool forced = c->kind == 2;
-    if (team) return forced ? launch_frozen_e<2, 1>(c, grid, P, A) : launch_frozen_e<0, 1>(c, grid, P, A);
-    return forced ? launch_frozen_e<2, 0>(c, grid, P, A) : launch_frozen_e<0, 0>(c, grid, P, A);
+    if (team) return forced ? launch_frozen_e<2, 1, PIECES>(c, grid, P, A) : launch_frozen_e<0, 1, PIECES>(c, grid, P, A);
+    return forced ? launch_frozen_e<2, 0, PIECES>(c, grid, P, A) : launch_frozen_e<0, 0, PIECES>(c, grid, P, A);
 }
 
 // the slab of a schedule cache with room for `cap` rows from a thread of the library's own (hipMalloc of 120 GB: 0.03 - 3 s);
@@ -460,6 +585,7 @@ static void frozen_alloc_in_thread(nk2d_frozen_cache* fc, int dev, size_t slab_b
                                    FrozenRow* old_frows) {
     if (fc->alloc_thread.joinable()) fc->alloc_thread.join();
     fc->alloc_state.store(1);
+    fc->alloc_is_pieces = false;
     fc->alloc_thread = std::thread([fc, dev, slab_bytes, cap, old_slab, old_rows, old_frows]() {
         bool ok = hipSetDevice(dev) == hipSuccess;
         if (old_slab) (void)hipFree(old_slab);
@@ -480,6 +606,98 @@ static void frozen_alloc_in_thread(nk2d_frozen_cache* fc, int dev, size_t slab_b
     });
 }
 
+// `count` more pieces of `piece_bytes` each from that thread (a cache in pieces): all of them or none -- on a refused piece
+// this request's pieces are given back and the state is 3.  The owner adopts them when the state says 2, none before
+static void frozen_alloc_pieces_in_thread(nk2d_frozen_cache* fc, int dev, size_t piece_bytes, size_t count, size_t piece_rows) {
+    if (fc->alloc_thread.joinable()) fc->alloc_thread.join();
+    fc->alloc_state.store(1);
+    fc->alloc_is_pieces = true;
+    fc->alloc_piece_rows = piece_rows;
+    fc->alloc_pieces.clear();
+    fc->alloc_thread = std::thread([fc, dev, piece_bytes, count]() {
+        bool ok = hipSetDevice(dev) == hipSuccess;
+        for (size_t k = 0; ok && k < count; ++k) {
+            double* p = nullptr;
+            ok = hipMalloc((void**)&p, piece_bytes) == hipSuccess;
+            if (ok) fc->alloc_pieces.push_back(p);
+        }
+        if (!ok) {
+            (void)hipGetLastError();
+            for (double* p : fc->alloc_pieces) (void)hipFree(p);
+            fc->alloc_pieces.clear();
+        }
+        fc->alloc_state.store(ok ? 2 : 3);
+    });
+}
+
+// what a thread was asked for: 1 not there yet, 3 refused, 0 nothing under way (any more: what it allocated is the cache's now)
+static int frozen_adopt(nk2d_ctx* c, nk2d_frozen_cache* fc) {
+    const int st = fc ? fc->alloc_state.load() : 0;
+    if (st == 0 || st == 1) return st;
+    if (fc->alloc_thread.joinable()) fc->alloc_thread.join();
+    fc->alloc_state.store(0);
+    if (st == 3) return 3;
+    if (fc->alloc_is_pieces) {
+        // (asked for with the rows per piece of the pieces held, if any: none is freed or added while a request is under way)
+        c->frozen_cache_piece_allocs += (int64_t)fc->alloc_pieces.size();
+        fc->pieces.insert(fc->pieces.end(), fc->alloc_pieces.begin(), fc->alloc_pieces.end());
+        fc->piece_rows = fc->alloc_piece_rows;
+        fc->alloc_pieces.clear();
+        return 0;
+    }
+    fc->slab = fc->alloc_slab; fc->rows_dev = fc->alloc_rows; fc->frows_dev = fc->alloc_frows; fc->cap_rows = fc->alloc_cap;
+    fc->alloc_slab = nullptr; fc->alloc_rows = nullptr; fc->alloc_frows = nullptr;
+    fc->C.KV = nullptr;     // (the tables' places are set at the build)
+    return 0;
+}
+
+// is the one-launch year made for this context and schedule?
+static bool frozen_eligible(const nk2d_ctx* c, const double* sched, int64_t n) {
+    const bool needs_state = c->kind == 1 || (c->kind == 2 && c->d.sms_nrec > 0 && c->d.sink_thres > 0.0);
+    if (!c->frozen_persistent || needs_state || c->hist_n != 0 || c->norm_hook || n < 1) return false;
+    // the cache holds the factorisation in double precision only: with option "factor_fp32" the recorded year read the single
+    // precision copies, and the one-launch year would not be the same discrete map (round-3 ADVICE) -- launch by launch then
+    if (c->factor_fp32) return false;
+    // (instantiated for one to four levels per lane, and for five to eight with linear sources)
+    if (c->E > c->frozen_persistent_max_e || c->E > 8 || (c->E > 4 && c->kind != 0)) return false;
+    // every row but the last must hand over to the next one (t_new == next t, whole step taken): the step-ending launch
+    // predicts the next attempt from this step's collocation polynomial
+    for (int64_t i = 0; i + 1 < n; ++i) {
+        const double* r = sched + i * NK2D_SCHED_WIDTH;
+        if (!(r[0] + r[2] == r[1] && r[NK2D_SCHED_WIDTH] == r[1] && r[NK2D_SCHED_WIDTH + 2] > 0.0 && (int)r[3] >= 1)) return false;
+    }
+    return (int)sched[(n - 1) * NK2D_SCHED_WIDTH + 3] >= 1;
+}
+
+// Options "frozen_cache_pieces" + "frozen_cache_early": the pieces for the `n` rows of the schedule a free-running year just
+// recorded are asked for NOW, from the thread whatever their size, so that they are there when the first product comes; the
+// tables are built where they always are, at the first frozen year.  (With the slab this was measured and taken out, see
+// below; pieces are what makes the request one the driver can serve beside other allocations -- or not: DESIGN 3.6.)
+int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
+    if (!c->frozen_cache_pieces || !c->frozen_cache_early || !sched || !frozen_eligible(c, sched, n)) return 0;
+    const size_t per_row = frozen_row_doubles(c), B = frozen_piece_rows(c), need = ((size_t)n + B - 1) / B;
+    const double bytes = 8.0 * (double)need * (double)B * (double)per_row;
+    if (bytes > c->frozen_cache_max_gb * 1.0e9) return 0;
+    nk2d_frozen_cache* fc = (nk2d_frozen_cache*)c->frozen_cache;
+    if (!fc) { fc = new nk2d_frozen_cache(); c->frozen_cache = fc; }
+    const int st = frozen_adopt(c, fc);
+    if (st == 1) return 0;
+    if (st == 3) { c->frozen_persistent = 0; return 0; }
+    if (fc->slab || (!fc->pieces.empty() && fc->piece_rows != B)) {
+        NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+        frozen_free_slab(fc);
+        frozen_free_pieces(fc);
+    }
+    if (fc->pieces.size() >= need) return 0;
+    size_t free_b = 0, total_b = 0;
+    NK2D_CHECK(c, hipMemGetInfo(&free_b, &total_b));
+    const double held = 8.0 * (double)fc->pieces.size() * (double)B * (double)per_row;
+    if (1.02 * bytes > 0.85 * ((double)free_b + held)) return 0;
+    frozen_alloc_pieces_in_thread(fc, c->dev, sizeof(double) * B * per_row, need - fc->pieces.size(), B);
+    c->frozen_cache_early_requests++;
+    return 0;
+}
+
 // (Asking for that slab EARLIER -- at the end of the free-running year whose steps the products will repeat, so that it is
 // there when the first product comes -- was built and measured in round 4 and taken out again: in a fresh process the
 // hipMalloc of 120 GB holds the driver for ~ 4 s, and the preconditioner's set-up, which lies between F(x) and the first
@@ -487,39 +705,40 @@ static void frozen_alloc_in_thread(nk2d_frozen_cache* fc, int dev, size_t slab_b
 // 9.34 s (profiles/r04_prealloc_experiment.log).  Beside the first products, which allocate nothing, the same request costs
 // them 0.1 - 1.2 s in all.)
 int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vector<char>* err_rows) {
-    const bool needs_state = c->kind == 1 || (c->kind == 2 && c->d.sms_nrec > 0 && c->d.sink_thres > 0.0);
-    if (!c->frozen_persistent || needs_state || c->hist_n != 0 || c->norm_hook || n < 1) return 1;
-    // the cache holds the factorisation in double precision only: with option "factor_fp32" the recorded year read the single
-    // precision copies, and the one-launch year would not be the same discrete map (round-3 ADVICE) -- launch by launch then
-    if (c->factor_fp32) return 1;
-    // (instantiated for one to four levels per lane, and for five to eight with linear sources)
-    if (c->E > c->frozen_persistent_max_e || c->E > 8 || (c->E > 4 && c->kind != 0)) return 1;
-    // every row but the last must hand over to the next one (t_new == next t, whole step taken): the step-ending launch
-    // predicts the next attempt from this step's collocation polynomial
-    for (int64_t i = 0; i + 1 < n; ++i) {
-        const double* r = sched + i * NK2D_SCHED_WIDTH;
-        if (!(r[0] + r[2] == r[1] && r[NK2D_SCHED_WIDTH] == r[1] && r[NK2D_SCHED_WIDTH + 2] > 0.0 && (int)r[3] >= 1)) return 1;
-    }
-    if ((int)sched[(n - 1) * NK2D_SCHED_WIDTH + 3] < 1) return 1;
+    if (!frozen_eligible(c, sched, n)) return 1;
     const size_t ntab = (size_t)c->ncol * NK2D_TAB * 64;
-    const double bytes = 8.0 * (double)n * (3.0 * c->kv_len + 5.0 * c->np + 3.0 * c->nv + 3.0 * ntab);
+    // the cache as pieces (option "frozen_cache_pieces"): `need` pieces of `B` rows; the limits apply to their sum
+    const bool want_pieces = c->frozen_cache_pieces != 0;
+    const size_t B = want_pieces ? frozen_piece_rows(c) : 0, need = want_pieces ? ((size_t)n + B - 1) / B : 0;
+    const double bytes = want_pieces ? 8.0 * (double)need * (double)B * (double)frozen_row_doubles(c)
+                                     : 8.0 * (double)n * (3.0 * c->kv_len + 5.0 * c->np + 3.0 * c->nv + 3.0 * ntab);
     if (bytes > c->frozen_cache_max_gb * 1.0e9) return 1;
-    {   // a slab a thread was asked for: not there yet (launch by launch), there (adopt it), or refused (never again)
-        nk2d_frozen_cache* fc = (nk2d_frozen_cache*)c->frozen_cache;
-        const int st = fc ? fc->alloc_state.load() : 0;
+    {   // what a thread was asked for: not there yet (launch by launch), there (adopt it), or refused (never again)
+        const int st = frozen_adopt(c, (nk2d_frozen_cache*)c->frozen_cache);
         if (st == 1) return 1;
-        if (st == 2 || st == 3) {
-            if (fc->alloc_thread.joinable()) fc->alloc_thread.join();
-            fc->alloc_state.store(0);
-            if (st == 3) { c->frozen_persistent = 0; return 1; }
-            fc->slab = fc->alloc_slab; fc->rows_dev = fc->alloc_rows; fc->frows_dev = fc->alloc_frows; fc->cap_rows = fc->alloc_cap;
-            fc->alloc_slab = nullptr; fc->alloc_rows = nullptr; fc->alloc_frows = nullptr;
-            fc->C.KV = nullptr;     // (the tables' places are set below)
+        if (st == 3) { c->frozen_persistent = 0; return 1; }
+    }
+    if (nk2d_frozen_cache* have = (nk2d_frozen_cache*)c->frozen_cache) {
+        // a context never holds a slab and pieces at once: the other form (and pieces of another size) go first
+        const bool drop_slab = want_pieces && have->slab;
+        const bool drop_pieces = !have->pieces.empty() && (!want_pieces || have->piece_rows != B);
+        if (drop_slab || drop_pieces) {
+            NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+            if (drop_slab) frozen_free_slab(have);
+            if (drop_pieces) frozen_free_pieces(have);
         }
     }
     {   // ... and never more than what the device has to spare right now (other contexts of the process, other tenants)
         nk2d_frozen_cache* have = (nk2d_frozen_cache*)c->frozen_cache;
-        if (!have || have->cap_rows < (size_t)n) {
+        if (want_pieces) {
+            const size_t held_n = have ? have->pieces.size() : 0;
+            if (held_n < need) {
+                size_t free_b = 0, total_b = 0;
+                NK2D_CHECK(c, hipMemGetInfo(&free_b, &total_b));
+                const double held = 8.0 * (double)held_n * (double)B * (double)frozen_row_doubles(c);
+                if (1.02 * bytes > 0.85 * ((double)free_b + held)) return 1;
+            }
+        } else if (!have || have->cap_rows < (size_t)n) {
             size_t free_b = 0, total_b = 0;
             NK2D_CHECK(c, hipMemGetInfo(&free_b, &total_b));
             const double held = have ? 8.0 * (double)have->cap_rows * (3.0 * c->kv_len + 5.0 * c->np + 3.0 * c->nv + 3.0 * ntab) : 0.0;
@@ -542,7 +761,51 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     DevP P = make_devp(c);
     if (fc->key != key || fc->n != n) {
         // ---- (re)build the cache for this schedule
-        if (fc->cap_rows < (size_t)n) {
+        if (want_pieces) {
+            const size_t per_row = frozen_row_doubles(c);
+            if (fc->pieces.size() < need) {
+                // more pieces, no headroom rows: what is there stays where it is
+                NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+                const size_t add = need - fc->pieces.size(), piece_bytes = sizeof(double) * B * per_row;
+                fc->key = 0; fc->n = 0;
+                if ((double)add * (double)piece_bytes > 8.0e9 && c->frozen_alloc_async) {
+                    // (piece by piece from the thread: launch by launch until all of them are there)
+                    frozen_alloc_pieces_in_thread(fc, c->dev, piece_bytes, add, B);
+                    return 1;
+                }
+                const size_t before = fc->pieces.size();
+                for (size_t k = 0; k < add; ++k) {
+                    double* p = nullptr;
+                    const hipError_t rc = hipMalloc((void**)&p, piece_bytes);
+                    if (rc != hipSuccess) {     // (this request's pieces are given back)
+                        for (size_t q = before; q < fc->pieces.size(); ++q) (void)hipFree(fc->pieces[q]);
+                        fc->pieces.resize(before);
+                        NK2D_CHECK(c, rc);
+                    }
+                    fc->pieces.push_back(p);
+                }
+                fc->piece_rows = B;
+                c->frozen_cache_piece_allocs += (int64_t)add;
+            }
+            if (fc->rows_cap < (size_t)n) {
+                NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+                if (fc->rows_dev) (void)hipFree(fc->rows_dev);
+                if (fc->frows_dev) (void)hipFree(fc->frows_dev);
+                fc->rows_dev = nullptr; fc->frows_dev = nullptr; fc->rows_cap = 0;
+                NK2D_CHECK(c, hipMalloc((void**)&fc->rows_dev, sizeof(CacheRow) * (size_t)n));
+                NK2D_CHECK(c, hipMalloc((void**)&fc->frows_dev, sizeof(FrozenRow) * (size_t)n));
+                fc->rows_cap = (size_t)n;
+            }
+            if (fc->pieces_dev_cap < fc->pieces.size()) {
+                NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+                if (fc->pieces_dev) (void)hipFree(fc->pieces_dev);
+                fc->pieces_dev = nullptr; fc->pieces_dev_cap = 0;
+                NK2D_CHECK(c, hipMalloc((void**)&fc->pieces_dev, sizeof(double*) * fc->pieces.size()));
+                fc->pieces_dev_cap = fc->pieces.size();
+            }
+            NK2D_CHECK(c, hipMemcpy(fc->pieces_dev, fc->pieces.data(), sizeof(double*) * fc->pieces.size(), hipMemcpyHostToDevice));
+            fc->C.KV = fc->C.J = fc->C.fr_inv = fc->C.fc_invr = fc->C.fc_invi = fc->C.fr_tab = fc->C.fc_tabr = fc->C.fc_tabi = nullptr;
+        } else if (fc->cap_rows < (size_t)n) {
             // ONE allocation for the whole cache, with room for the longer schedules of later Newton iterates: giving 100 GB
             // back and asking for them again costs seconds (measured inside a Newton run: 4.4 s), the first request 0.03 - 0.8 s
             NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
@@ -578,7 +841,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             NK2D_CHECK(c, hipMalloc((void**)&fc->frows_dev, sizeof(FrozenRow) * cap));
             fc->cap_rows = cap;
         }
-        if (fc->C.KV != fc->slab || fc->C.nv != c->nv) {   // (a new slab: the tables' places in it)
+        if (!want_pieces && (fc->C.KV != fc->slab || fc->C.nv != c->nv)) {   // (a new slab: the tables' places in it)
             const size_t cap = fc->cap_rows;
             double* p = fc->slab;
             fc->C.KV = p; p += cap * 3 * c->kv_len;
@@ -604,7 +867,8 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             times[3] = t_jac;
             for (int k = 0; k < 4; ++k) {
                 nk2d_host_interp(4, c->d.bld_tvals, c->d.bld_fvals, times[k], &R.v.frac[k]);
-                R.v.out[k] = (k < 3) ? fc->C.KV + ((size_t)i * 3 + k) * c->kv_len : nullptr;
+                if (want_pieces) R.v.out[k] = (k < 3) ? fc->pieces[(size_t)i / B] + (((size_t)i % B) * 3 + k) * c->kv_len : nullptr;
+                else R.v.out[k] = (k < 3) ? fc->C.KV + ((size_t)i * 3 + k) * c->kv_len : nullptr;
             }
             vmix_forcing_args(c, 3, times, R.v);
             R.v.bldmin = c->d.bldepth_min; R.v.y0 = c->d.vmix_log_shallow; R.v.y1 = c->d.vmix_log_deep; R.v.hw = c->d.vmix_half_width;
@@ -629,7 +893,20 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
         NK2D_CHECK(c, hipMemcpyAsync(fc->rows_dev, rows.data(), sizeof(CacheRow) * (size_t)n, hipMemcpyHostToDevice, nk2d_s(c)));
         NK2D_CHECK(c, hipMemcpyAsync(fc->frows_dev, fc->frows.data(), sizeof(FrozenRow) * (size_t)n, hipMemcpyHostToDevice, nk2d_s(c)));
         NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));    // `rows` leaves scope
-        {
+        if (want_pieces) {
+            CachePiecePtrs CP;
+            CP.C = fc->C;
+            CP.T = frozen_piece_tab(c, fc);
+            const long long tasks = 4LL * c->ny * n;
+            NK2D_DISPATCH_E(c->E, hipLaunchKernelGGL((k_cache_planes<EE, 1>), dim3((unsigned)((tasks + 3) / 4)), dim3(NK2D_BLOCK), 0, nk2d_s(c),
+                                                      P, fc->rows_dev, CP, (int)n));
+            NK2D_CHECK(c, hipGetLastError());
+            const long long ftasks = 2LL * c->ncol * n;
+            NK2D_DISPATCH_EK(c->E, c->kind, hipLaunchKernelGGL((k_cache_factor<EE, KK, 1>), dim3((unsigned)((ftasks + 3) / 4)), dim3(NK2D_BLOCK), 0,
+                                                               nk2d_s(c), P, fc->rows_dev, CP, (int)n));
+            NK2D_CHECK(c, hipGetLastError());
+            c->st.nlaunch += 2;
+        } else {
             const long long tasks = 4LL * c->ny * n;
             NK2D_DISPATCH_E(c->E, hipLaunchKernelGGL(k_cache_planes<EE>, dim3((unsigned)((tasks + 3) / 4)), dim3(NK2D_BLOCK), 0, nk2d_s(c),
                                                       P, fc->rows_dev, fc->C, (int)n));
@@ -643,6 +920,12 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
         fc->key = key;
         fc->n = n;
         c->frozen_cache_builds++;
+    }
+    // a cache in pieces: every piece that covers rows < n must be there -- the kernel never looks at a missing one
+    if (want_pieces) {
+        if (fc->piece_rows != B || fc->pieces.size() < need || !fc->pieces_dev || fc->pieces_dev_cap < need) return 1;
+        for (size_t p = 0; p < need; ++p)
+            if (!fc->pieces[p]) return 1;
     }
     // ---- the year
     if (!c->YR_OUT) {
@@ -658,7 +941,8 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
         c->YR_REC = nullptr;
     }
     NK2D_CHECK(c, hipMemsetAsync(c->YR_SYNC, 0, yr_sync_bytes(c), nk2d_s(c)));
-    FrozenArgs A = {};
+    FrozenPieceArgs A = {};      // (the slab flavour takes its FrozenArgs part)
+    if (want_pieces) A.T = frozen_piece_tab(c, fc);
     A.Y = c->Y; A.YOLD = c->YOLD; A.Z = c->Z; A.ZN = c->ZN; A.W = c->W; A.F = c->F;
     A.BR = c->BR; A.BCR = c->BCR; A.BCI = c->BCI;
     for (int i = 0; i < 2; ++i) { A.XR[i] = c->XR[i]; A.XCR[i] = c->XCR[i]; A.XCI[i] = c->XCI[i]; }
@@ -708,7 +992,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             explicit Turn(int w) : waves(w) { nk2d_turn_take(waves); }
             ~Turn() { nk2d_turn_give(waves); }
         } turn(team ? 4 * c->ncol : c->ncol);
-        rc = launch_frozen(c, team, dim3(nblk), P, A);
+        rc = want_pieces ? launch_frozen<1>(c, team, dim3(nblk), P, A) : launch_frozen<0>(c, team, dim3(nblk), P, static_cast<FrozenArgs&>(A));
         if (rc == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return 1; }
         NK2D_CHECK(c, rc);
         NK2D_CHECK(c, hipEventRecord(c->yr_ev[1], nk2d_s(c)));

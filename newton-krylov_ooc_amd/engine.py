@@ -212,6 +212,14 @@ class ModuleEngine:
             self.set_option("stream_hist", float(os.environ["NK2D_STREAM_HIST"]))
         if "NK2D_STREAM_HIST_MB" in os.environ:
             self.set_option("stream_hist_mb", float(os.environ["NK2D_STREAM_HIST_MB"]))
+        # the schedule cache of the one-launch frozen year as a list of pieces instead of one slab, a piece's size in MiB, and the
+        # request for the pieces at the end of the year that records the schedule (csrc/nk2d_frozen.hip)
+        if "NK2D_FROZEN_CACHE_PIECES" in os.environ:
+            self.set_option("frozen_cache_pieces", float(os.environ["NK2D_FROZEN_CACHE_PIECES"]))
+        if "NK2D_FROZEN_CACHE_PIECE_MB" in os.environ:
+            self.set_option("frozen_cache_piece_mb", float(os.environ["NK2D_FROZEN_CACHE_PIECE_MB"]))
+        if "NK2D_FROZEN_CACHE_EARLY" in os.environ:
+            self.set_option("frozen_cache_early", float(os.environ["NK2D_FROZEN_CACHE_EARLY"]))
         # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_TWO_ENDED" in os.environ:
             self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
