@@ -226,12 +226,18 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    schedule of n rows needs ceil(n / B) pieces, pieces are kept from schedule to schedule and only added to, the limits above
    apply to their sum, the thread allocates piece by piece and all its pieces are adopted together, switching the option frees
    the other form first; "frozen_cache_early" 0, default, or 1, with pieces only: nk2d_comp_fcn with `record` asks the thread for
-   the pieces of the schedule it recorded when the year ends, whatever their size).  Same device functions, bit-identical results; a year that does not pass the Newton check, or a
+   the pieces of the schedule it recorded when the year ends, whatever their size; "frozen_cache_lean" 0, default, 1 or 2, opt-in,
+   read when a cache is (re)built: the cache holds the mixing and Jacobian planes only -- 8 n (3 kv_len + 5 np) bytes, about 30 % of
+   the full rows, to which every limit above then applies -- and the year factorises in the first phase of every step, on one
+   row's worth of factor tables; 1: every schedule cache of the context, 2: only a schedule whose full cache "frozen_cache_gb" or
+   the 85 % rule would refuse; composes with pieces, switching lean <-> full frees the other form first, any other value is an
+   error, not taken with "factor_fp32").  Same device functions, bit-identical results; a year that does not pass the Newton check, or a
    barrier that times out, is handed to the launch-per-phase path.  Counters by name: "frozen_persistent_years",
    "frozen_team_years" (of them: a four-wave team per column), "frozen_cache_bytes",
    "frozen_launch_us" (device time of those launches), "frozen_cache_pending" (1 while a thread allocates a large cache or pieces),
    "frozen_cache_pieces" (pieces held; "frozen_cache_bytes" is then their sum), "frozen_cache_piece_allocs" (pieces allocated
-   so far), "frozen_cache_early_requests" (early requests made),
+   so far), "frozen_cache_early_requests" (early requests made), "frozen_cache_lean" (1 while the cache held is lean),
+   "frozen_lean_years" (one-launch years run on a lean cache; also counted in "frozen_persistent_years"),
    "frozen_cache_builds", "frozen_fallbacks", "frozen_resumes"; of the host-side controller: "spec_launches_dropped",
    "spec_front_launches_dropped", "err_estimates_queued", "err_estimates_dropped" (work queued ahead of a verdict); of the
    preconditioner (option "pc_two_ended"): "pc_setup_rounds" (dependent inversion rounds of the last block elimination: ny,

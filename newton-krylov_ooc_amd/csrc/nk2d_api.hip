@@ -220,6 +220,13 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
         c->frozen_cache_pieces = (int)value;
         return 0;
     }
+    if (key == "frozen_cache_lean") {
+        // the schedule cache without the factor tables (nk2d_frozen.hip): the one-launch year factorises in the first phase of every
+        // step; 2: only where the full cache would be refused.  Taken when a cache is (re)built
+        if (value != 0.0 && value != 1.0 && value != 2.0) return nk2d_fail(c, "nk2d_set_option: frozen_cache_lean is 0, 1 or 2");
+        c->frozen_cache_lean = (int)value;
+        return 0;
+    }
     if (key == "frozen_cache_piece_mb") {
         if (!(value > 0.0) || !std::isfinite(value)) return nk2d_fail(c, "nk2d_set_option: frozen_cache_piece_mb must be > 0");
         c->frozen_cache_piece_mb = value;
@@ -594,6 +601,9 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_cache_piece_mb = 1024.0;
     c->frozen_cache_piece_rows = 0;
     c->frozen_cache_early = 0;
+    c->frozen_cache_lean = 0;
+    c->frozen_lean_years = 0;
+    c->frozen_lean_mem_key = 0;
     c->frozen_cache_piece_allocs = c->frozen_cache_early_requests = 0;
     c->frozen_coef_lds = 15;
     c->frozen_by_column = 1;
@@ -1137,6 +1147,8 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_cache_pending") v = nk2d_frozen_cache_pending(c);
     else if (key == "frozen_cache_bytes") v = nk2d_frozen_cache_bytes(c);
     else if (key == "frozen_cache_pieces") v = nk2d_frozen_cache_npieces(c);
+    else if (key == "frozen_cache_lean") v = nk2d_frozen_cache_is_lean(c);
+    else if (key == "frozen_lean_years") v = c->frozen_lean_years;
     else if (key == "frozen_cache_piece_allocs") v = nk2d_frozen_cache_piece_allocs(c);
     else if (key == "frozen_cache_early_requests") v = c->frozen_cache_early_requests;
     else if (key == "frozen_fallbacks") v = c->frozen_fallbacks;

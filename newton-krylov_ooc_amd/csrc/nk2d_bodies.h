@@ -2004,6 +2004,8 @@ struct CachePtrs {
     double *fr_tab, *fc_tabr, *fc_tabi;                 // [n][ncol * NK2D_TAB * 64]
     size_t kv_len, np, nv, ntab;
 };
+// A LEAN cache (option "frozen_cache_lean") holds KV and J only: the six factor-table pointers are then ONE row's worth of tables
+// ([nv] / [ncol * NK2D_TAB * 64], owned by the cache), which the first phase of every row of the year fills for its own column
 
 // The same cache as a list of equally sized PIECES (option "frozen_cache_pieces"): piece p holds rows [p rows, (p + 1) rows),
 // laid out inside as a slab with room for `rows` rows -- the eight tables in CachePtrs' order at fixed offsets (in doubles)
@@ -2197,6 +2199,7 @@ struct FrozenRow {
     int n_iter, m;               // simplified-Newton iterations, sweeps per solve
     double h;                    // step size
     int err;                     // 1: SciPy's error estimate of this step is evaluated too (its partials to row 3 i + 2 of STEP_PART)
+    double cre, ccr, cci;        // shifts of the row's line factorisation (h_lu): what the LEAN year factorises with in the row's first phase
 };
 
 struct FrozenArgs {

@@ -144,6 +144,10 @@ struct nk2d_ctx {
     int frozen_cache_pieces;          // 0 (default): the slab, 1: pieces
     double frozen_cache_piece_mb;     // option "frozen_cache_piece_mb": size of a piece in MiB (rows per piece = floor of it over a row's bytes, at least 1)
     int64_t frozen_cache_piece_rows;  // option "frozen_cache_piece_rows": rows per piece directly (0: from the size in MiB)
+    // option "frozen_cache_lean": the schedule cache holds the planes only, the one-launch year factorises in the first phase of every step
+    int frozen_cache_lean;            // 0 (default): the full cache, 1: lean, 2: lean where the full cache would be refused
+    int64_t frozen_lean_years;        // lean one-launch years run (also counted in frozen_persistent_years)
+    uint64_t frozen_lean_mem_key;     // mode 2: the schedule whose full cache the 85 % rule refused last
     int frozen_cache_early;           // option "frozen_cache_early": with pieces, the year that records a schedule asks for its pieces when it ends
     int64_t frozen_cache_piece_allocs, frozen_cache_early_requests;   // counters: pieces allocated so far, early requests made
     uint64_t frozen_seen_key; int frozen_seen_years;   // the schedule last seen by nk2d_frozen_persistent and its years so far
@@ -646,6 +650,7 @@ int64_t nk2d_frozen_cache_piece_allocs(const nk2d_ctx* c);
 // option "frozen_cache_early": the pieces of the schedule a free-running year just recorded, asked for from a thread
 int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n);
 int64_t nk2d_frozen_cache_bytes(const nk2d_ctx* c);
+int nk2d_frozen_cache_is_lean(const nk2d_ctx* c);      // 1 while the cache the context holds is lean (option "frozen_cache_lean")
 void nk2d_frozen_cache_free(nk2d_ctx* c);
 int nk2d_prof_window_begin(nk2d_ctx* c);
 int nk2d_prof_window_end(nk2d_ctx* c);

@@ -68,6 +68,25 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_cache_factor(DevP P, const Cache
     factor_body<E, KIND>(P, A, rem, lane);
 }
 
+// The factorising first phase of a row of the LEAN one-launch year, a wave per column: newton_fused_body with FACTOR = 1.  Of
+// what the year keeps in LDS it takes the coefficients and W (W lives nowhere else); the step block, a copy of what the cache
+// row holds, it reads from memory like the command stream's factorising phase -- the same values.  Behind it the column's
+// pivots of the real system, which it has just written, go to the wave's own LDS slot for the phases that follow (bit 8).
+// (Three and more levels per lane; below that nothing of the year is in LDS and the phase is the plain factorising body.)
+template <int E, int KIND, int MPX, int FINAL>
+__device__ __forceinline__ void frozen_factor_phase(const DevP& P, const FusedArgs& FA, int wave, int lane, const FinalArgs* fin, const LdsSrc* L,
+                                                    int coef_lds, bool w_in_lds, double* piv_lds) {
+    if (w_in_lds) newton_fused_body<E, KIND, 1, 1, MPX, FINAL, 3>(P, FA, wave, lane, fin, L);
+    else if (coef_lds) newton_fused_body<E, KIND, 1, 1, MPX, FINAL, 1>(P, FA, wave, lane, fin, L);
+    else newton_fused_body<E, KIND, 1, 1, MPX, FINAL>(P, FA, wave, lane, fin);
+    if (piv_lds) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (the wave's own stores, read back by itself)
+        double v[E];
+        load_col<E>(FA.sw.fr_inv, wave, lane, v);
+        w_lds_put<E>(piv_lds, 0, lane, v);
+    }
+}
+
 // TEAM = 1: a workgroup is ONE column, its four waves the team of newton_team_body (a stage tendency each on three of them,
 // the complex system on the fourth, exchanges through LDS): the phase of a small grid is the dependent arithmetic of one
 // column's Newton iteration, and the team cuts that chain (three tendencies one after the other, then the real and the
@@ -75,7 +94,12 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_cache_factor(DevP P, const Cache
 // PIECES = 1: the cache is a list of pieces (option "frozen_cache_pieces", FrozenPieceArgs): once per row the piece's base comes
 // from the device table by one scalar load and the row's eight table addresses are formed in scalar registers; the phases
 // read them as the slab flavour reads its own.  Everything else is the one body.
-template <int E, int KIND, int TEAM = 0, int PIECES = 0>
+// LEAN = 1: the cache holds the planes only (option "frozen_cache_lean"): the six factor-table pointers of A.C are ONE row's
+// worth of tables, and the first phase of every row is the factorising instantiation of its body (FACTOR = 1, what the
+// launch-per-phase path runs at every "LU" event) with the row's shifts: it leaves pivots and PCR tables of the wave's own
+// column there, and the row's later phases -- the error estimate included -- read them as they read a full cache's.  A
+// column's tables are written and read by its own workgroup only: nothing of them crosses the hand-over.
+template <int E, int KIND, int TEAM = 0, int PIECES = 0, int LEAN = 0>
 __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typename FrozenArgOf<PIECES>::type A) {
     constexpr int XCD = 0, NB = 1;      // (rounds 2 - 3 also had all workgroups on one XCD and a grid barrier between the phases)
     __shared__ int lds_ok;
@@ -213,7 +237,18 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typena
                 FA.st.br = A.BR; FA.st.bcr = A.BCR; FA.st.bci = A.BCI;
                 FA.st.nv = nv; FA.st.mreal = R.mreal; FA.st.mcr = R.mcr; FA.st.mci = R.mci;
                 FA.sw.JL = J; FA.sw.JU = J + A.C.np; FA.sw.JS = J + 2 * A.C.np; FA.sw.JN = J + 3 * A.C.np; FA.sw.JC = J + 4 * A.C.np;
-                if constexpr (PIECES) {
+                // LEAN: this phase factorises (the first of the row); the one row of tables
+                const bool fac = LEAN != 0 && k == 0 && it == 0;
+                // (The factorising bodies read the grid's parameters where the launch put them, in the kernel-argument segment, whose
+                // first argument P is: with them reading the kernel's own copy of P, the compiler -- ROCm 7.2's clang 22, instcombine's
+                // rewrite of an argument copy that is only read -- crashes on the forced module at one level per lane.  Same values.)
+                const DevP& PK = *(const DevP*)__builtin_amdgcn_kernarg_segment_ptr();
+                (void)PK;
+                if constexpr (LEAN) {
+                    FA.sw.fr_inv = A.C.fr_inv; FA.sw.fc_invr = A.C.fc_invr; FA.sw.fc_invi = A.C.fc_invi;
+                    FA.sw.fr_tab = A.C.fr_tab; FA.sw.fc_tabr = A.C.fc_tabr; FA.sw.fc_tabi = A.C.fc_tabi;
+                    FA.sw.cre = R.cre; FA.sw.ccr = R.ccr; FA.sw.cci = R.cci;
+                } else if constexpr (PIECES) {
                     FA.sw.fr_inv = T.fr_inv; FA.sw.fc_invr = T.fc_invr; FA.sw.fc_invi = T.fc_invi;
                     FA.sw.fr_tab = T.fr_tab; FA.sw.fc_tabr = T.fc_tabr; FA.sw.fc_tabi = T.fc_tabi;
                 } else {
@@ -244,11 +279,13 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typena
                             load_col<E, MPX>(src, wave % P.ny, lane, v);
                             w_lds_put<E>(step_lds, r, lane, v);
                         }
+                        if constexpr (!LEAN) {
                         if (piv_in_lds && col_wave) {
                             double v[E];
                             load_col<E>(FA.sw.fr_inv, wave, lane, v);
                             w_lds_put<E>(my_piv, 0, lane, v);
                         }
+                        }       // (LEAN: the pivots do not exist yet -- filled behind the factorising phase below)
                         lds_step = i;
                         __syncthreads();
                     }
@@ -260,8 +297,15 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typena
                     Fin.x0 = R.x0; Fin.x1 = R.x1; Fin.x2 = R.x2;
                     Fin.nblk_cols = 0;
                     if constexpr (TEAM) {
-                        if (col_wave)
+                        if constexpr (LEAN) {
+                            if (col_wave && fac)
+                                newton_team_body<E, KIND, 1, 1, 4, 1, MPX>(PK, FA, *reinterpret_cast<TeamLds<E, 3>*>(team_lds), wave, tw, lane, &Fin);
+                        }
+                        if (col_wave && !fac)
                             newton_team_body<E, KIND, 0, 1, 4, 1, MPX>(P, FA, *reinterpret_cast<TeamLds<E, 3>*>(team_lds), wave, tw, lane, &Fin);
+                    } else if (col_wave && fac) {
+                        if constexpr (LEAN && COEF_LDS) frozen_factor_phase<E, KIND, MPX, 1>(PK, FA, wave, lane, &Fin, &L, A.coef_lds, w_in_lds, piv_in_lds ? my_piv : nullptr);
+                        else if constexpr (LEAN) newton_fused_body<E, KIND, 1, 1, MPX, 1>(PK, FA, wave, lane, &Fin);
                     } else if (col_wave) {
                         bool taken = false;
                         if constexpr (KIND == 0 && E <= 2) {
@@ -279,8 +323,15 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typena
                     if (do_stage) swapZ ^= 1;
                 } else {
                     if constexpr (TEAM) {
-                        if (col_wave)
+                        if constexpr (LEAN) {
+                            if (col_wave && fac)
+                                newton_team_body<E, KIND, 1, 1, 4, 0, MPX>(PK, FA, *reinterpret_cast<TeamLds<E, 3>*>(team_lds), wave, tw, lane, nullptr);
+                        }
+                        if (col_wave && !fac)
                             newton_team_body<E, KIND, 0, 1, 4, 0, MPX>(P, FA, *reinterpret_cast<TeamLds<E, 3>*>(team_lds), wave, tw, lane, nullptr);
+                    } else if (col_wave && fac) {
+                        if constexpr (LEAN && COEF_LDS) frozen_factor_phase<E, KIND, MPX, 0>(PK, FA, wave, lane, nullptr, &L, A.coef_lds, w_in_lds, piv_in_lds ? my_piv : nullptr);
+                        else if constexpr (LEAN) newton_fused_body<E, KIND, 1, 1, MPX, 0>(PK, FA, wave, lane);
                     } else if (col_wave) {
                         bool taken = false;
                         if constexpr (KIND == 0 && E <= 2) {
@@ -304,8 +355,8 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typena
             if (col_wave && (!TEAM || tw == 0)) {
                 ErrArgs EA = {};
                 EA.sw.JL = J; EA.sw.JU = J + A.C.np; EA.sw.JS = J + 2 * A.C.np; EA.sw.JN = J + 3 * A.C.np; EA.sw.JC = J + 4 * A.C.np;
-                EA.sw.fr_inv = PIECES ? T.fr_inv : A.C.fr_inv + (size_t)i * nv;
-                EA.sw.fr_tab = PIECES ? T.fr_tab : A.C.fr_tab + (size_t)i * A.C.ntab;
+                EA.sw.fr_inv = LEAN ? A.C.fr_inv : (PIECES ? T.fr_inv : A.C.fr_inv + (size_t)i * nv);
+                EA.sw.fr_tab = LEAN ? A.C.fr_tab : (PIECES ? T.fr_tab : A.C.fr_tab + (size_t)i * A.C.ntab);
                 EA.sw.xr_old = A.XR[0]; EA.sw.xr_new = A.XR[1];
                 EA.f = A.F; EA.z = FZ_Z; EA.y = FZ_Y; EA.nv = nv; EA.h = R.h;
                 EA.part = A.STEP_PART + (size_t)(3 * i + 2) * P.ncol;
@@ -391,18 +442,24 @@ struct nk2d_frozen_cache {
     std::vector<double*> alloc_pieces;  // what the thread allocated (valid with alloc_state 2 and alloc_is_pieces)
     size_t alloc_piece_rows = 0;
     bool alloc_is_pieces = false;
+    // option "frozen_cache_lean": the slab / the pieces hold the planes only (KV, J) -- never both forms at once -- and
+    // `lean_tab` is the ONE row of factor tables (3 nv + 3 ntab doubles, allocated once) that the year's kernel fills row by row
+    bool lean = false;
+    bool alloc_lean = false;            // the form a thread's allocation was asked for
+    double* lean_tab = nullptr;
+    size_t lean_tab_doubles = 0;
 };
 
-// doubles of a row of the cache
-static size_t frozen_row_doubles(const nk2d_ctx* c) {
+// doubles of a row of the cache (lean: the planes only)
+static size_t frozen_row_doubles(const nk2d_ctx* c, bool lean) {
     const size_t ntab = (size_t)c->ncol * NK2D_TAB * 64;
-    return 3 * c->kv_len + 5 * c->np + 3 * c->nv + 3 * ntab;
+    return 3 * c->kv_len + 5 * c->np + (lean ? 0 : 3 * c->nv + 3 * ntab);
 }
 
 // rows per piece: option "frozen_cache_piece_rows", or what fits "frozen_cache_piece_mb" MiB (at least one)
-static size_t frozen_piece_rows(const nk2d_ctx* c) {
+static size_t frozen_piece_rows(const nk2d_ctx* c, bool lean) {
     if (c->frozen_cache_piece_rows > 0) return (size_t)c->frozen_cache_piece_rows;
-    const double fit = std::floor(c->frozen_cache_piece_mb * 1048576.0 / (8.0 * (double)frozen_row_doubles(c)));
+    const double fit = std::floor(c->frozen_cache_piece_mb * 1048576.0 / (8.0 * (double)frozen_row_doubles(c, lean)));
     return fit >= 1.0 ? (size_t)std::min(fit, 1.0e9) : (size_t)1;
 }
 
@@ -440,6 +497,8 @@ static uint64_t sched_key(const double* sched, int64_t n) {
 
 // what a schedule cache (and a command tape, option "frozen_tape") is kept for: the schedule, the context's fingerprint and the
 // error-estimate stride
+// (a LEAN cache of the same schedule has another key: a full cache is never read as a lean one)
+static const uint64_t FROZEN_LEAN_KEY = 0xC2B2AE3D27D4EB4Full;
 uint64_t nk2d_frozen_key(const nk2d_ctx* c, const double* sched, int64_t n) {
     return sched_key(sched, n) ^ (uint64_t)nk2d_fingerprint(c) ^ ((uint64_t)(c->frozen_err_check + 1) * 0x9E3779B97F4A7C15ull);
 }
@@ -451,6 +510,10 @@ static PieceTab frozen_piece_tab(const nk2d_ctx* c, const nk2d_frozen_cache* fc)
     T.base = fc->pieces_dev;
     T.rows = (int)B;
     T.oJ = B * 3 * c->kv_len;
+    if (fc->lean) {     // (a piece ends behind J: the offsets of the absent tables are unused)
+        T.ofr = T.ofcr = T.ofci = T.otr = T.otcr = T.otci = 0;
+        return T;
+    }
     T.ofr = T.oJ + B * 5 * c->np;
     T.ofcr = T.ofr + B * c->nv;
     T.ofci = T.ofcr + B * c->nv;
@@ -470,10 +533,15 @@ int nk2d_frozen_cache_pending(const nk2d_ctx* c) {
 int64_t nk2d_frozen_cache_bytes(const nk2d_ctx* c) {
     const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
     if (!fc) return 0;
-    if (!fc->pieces.empty()) return (int64_t)(8 * fc->pieces.size() * fc->piece_rows * frozen_row_doubles(c));
+    if (!fc->pieces.empty()) return (int64_t)(8 * fc->pieces.size() * fc->piece_rows * frozen_row_doubles(c, fc->lean));
     if (!fc->slab) return 0;
-    const size_t ntab = (size_t)c->ncol * NK2D_TAB * 64;
-    return (int64_t)(8 * fc->cap_rows * (3 * c->kv_len + 5 * c->np + 3 * c->nv + 3 * ntab));
+    return (int64_t)(8 * fc->cap_rows * frozen_row_doubles(c, fc->lean));
+}
+
+// 1 while the schedule cache this context holds is lean (option "frozen_cache_lean")
+int nk2d_frozen_cache_is_lean(const nk2d_ctx* c) {
+    const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
+    return (fc && fc->lean && (fc->slab || !fc->pieces.empty())) ? 1 : 0;
 }
 
 // pieces allocated for this context so far: those booked, and those a thread has finished allocating and the owner has not
@@ -502,6 +570,7 @@ void nk2d_frozen_cache_free(nk2d_ctx* c) {
     }
     frozen_free_pieces(fc);
     frozen_free_slab(fc);
+    if (fc->lean_tab) (void)hipFree(fc->lean_tab);
     delete fc;
     c->frozen_cache = nullptr;
 }
@@ -542,7 +611,7 @@ static hipError_t launch_resident(nk2d_ctx* c, K kernel, dim3 grid, dim3 block, 
     return hipGetLastError();
 }
 
-template <int E, int KIND, int TEAM, int PIECES>
+template <int E, int KIND, int TEAM, int PIECES, int LEAN>
 static hipError_t launch_frozen_one(nk2d_ctx* c, dim3 grid, DevP& P, typename FrozenArgOf<PIECES>::type& A) {
     // a team per column: the workgroup IS the column.  A wave per column: option "frozen_wpb" adjacent columns of one tracer to
     // a workgroup (its waves move in lock step, its neighbours are the workgroups to the left and right), or -- by_column --
@@ -550,42 +619,43 @@ static hipError_t launch_frozen_one(nk2d_ctx* c, dim3 grid, DevP& P, typename Fr
     const int wpb = TEAM ? NK2D_WAVES_PER_BLOCK : std::max(1, std::min(NK2D_WAVES_PER_BLOCK, c->frozen_wpb));
     const dim3 g = TEAM ? grid : dim3((unsigned)((c->ncol + wpb - 1) / wpb));
     if (!TEAM && E >= 3 && A.by_column)
-        return launch_resident(c, k_frozen_persistent<E, KIND, TEAM, PIECES>, dim3((unsigned)c->ny), dim3(64 * c->tc), P, A,
+        return launch_resident(c, k_frozen_persistent<E, KIND, TEAM, PIECES, LEAN>, dim3((unsigned)c->ny), dim3(64 * c->tc), P, A,
                                sizeof(double) * frozen_lds_doubles(E, A.coef_lds, true, c->tc));
     const size_t lds = (!TEAM && E >= 3 && A.coef_lds) ? sizeof(double) * frozen_lds_doubles(E, A.coef_lds, false, wpb) : 0;
-    return launch_resident(c, k_frozen_persistent<E, KIND, TEAM, PIECES>, g, dim3(64 * wpb), P, A, lds);
+    return launch_resident(c, k_frozen_persistent<E, KIND, TEAM, PIECES, LEAN>, g, dim3(64 * wpb), P, A, lds);
 }
-template <int KIND, int TEAM, int PIECES>
+template <int KIND, int TEAM, int PIECES, int LEAN>
 static hipError_t launch_frozen_e(nk2d_ctx* c, dim3 grid, DevP& P, typename FrozenArgOf<PIECES>::type& A) {
     switch (c->E) {
-        case 1: return launch_frozen_one<1, KIND, TEAM, PIECES>(c, grid, P, A);
-        case 2: return launch_frozen_one<2, KIND, TEAM, PIECES>(c, grid, P, A);
+        case 1: return launch_frozen_one<1, KIND, TEAM, PIECES, LEAN>(c, grid, P, A);
+        case 2: return launch_frozen_one<2, KIND, TEAM, PIECES, LEAN>(c, grid, P, A);
         // three and four levels per lane: a wave per column (all module kinds)
-        case 3: if constexpr (!TEAM) return launch_frozen_one<3, KIND, 0, PIECES>(c, grid, P, A); else break;
-        case 4: if constexpr (!TEAM) return launch_frozen_one<4, KIND, 0, PIECES>(c, grid, P, A); else break;
+        case 3: if constexpr (!TEAM) return launch_frozen_one<3, KIND, 0, PIECES, LEAN>(c, grid, P, A); else break;
+        case 4: if constexpr (!TEAM) return launch_frozen_one<4, KIND, 0, PIECES, LEAN>(c, grid, P, A); else break;
         // five to eight levels per lane (up to 512 levels): a wave per column, linear sources
-        case 5: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<5, 0, 0, PIECES>(c, grid, P, A); else break;
-        case 6: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<6, 0, 0, PIECES>(c, grid, P, A); else break;
-        case 7: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<7, 0, 0, PIECES>(c, grid, P, A); else break;
-        case 8: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<8, 0, 0, PIECES>(c, grid, P, A); else break;
+        case 5: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<5, 0, 0, PIECES, LEAN>(c, grid, P, A); else break;
+        case 6: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<6, 0, 0, PIECES, LEAN>(c, grid, P, A); else break;
+        case 7: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<7, 0, 0, PIECES, LEAN>(c, grid, P, A); else break;
+        case 8: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<8, 0, 0, PIECES, LEAN>(c, grid, P, A); else break;
         default: break;
     }
     return hipErrorInvalidValue;
 }
-template <int PIECES>
+template <int PIECES, int LEAN>
 static hipError_t launch_frozen(nk2d_ctx* c, bool team, dim3 grid, DevP& P, typename FrozenArgOf<PIECES>::type& A) {
     const bool forced = c->kind == 2;
-    if (team) return forced ? launch_frozen_e<2, 1, PIECES>(c, grid, P, A) : launch_frozen_e<0, 1, PIECES>(c, grid, P, A);
-    return forced ? launch_frozen_e<2, 0, PIECES>(c, grid, P, A) : launch_frozen_e<0, 0, PIECES>(c, grid, P, A);
+    if (team) return forced ? launch_frozen_e<2, 1, PIECES, LEAN>(c, grid, P, A) : launch_frozen_e<0, 1, PIECES, LEAN>(c, grid, P, A);
+    return forced ? launch_frozen_e<2, 0, PIECES, LEAN>(c, grid, P, A) : launch_frozen_e<0, 0, PIECES, LEAN>(c, grid, P, A);
 }
 
 // the slab of a schedule cache with room for `cap` rows from a thread of the library's own (hipMalloc of 120 GB: 0.03 - 3 s);
 // what the cache held before is given back by that thread first.  alloc_state 1 while it runs, 2 / 3 when done / refused
 static void frozen_alloc_in_thread(nk2d_frozen_cache* fc, int dev, size_t slab_bytes, size_t cap, double* old_slab, CacheRow* old_rows,
-                                   FrozenRow* old_frows) {
+                                   FrozenRow* old_frows, bool lean) {
     if (fc->alloc_thread.joinable()) fc->alloc_thread.join();
     fc->alloc_state.store(1);
     fc->alloc_is_pieces = false;
+    fc->alloc_lean = lean;
     fc->alloc_thread = std::thread([fc, dev, slab_bytes, cap, old_slab, old_rows, old_frows]() {
         bool ok = hipSetDevice(dev) == hipSuccess;
         if (old_slab) (void)hipFree(old_slab);
@@ -608,10 +678,11 @@ static void frozen_alloc_in_thread(nk2d_frozen_cache* fc, int dev, size_t slab_b
 
 // `count` more pieces of `piece_bytes` each from that thread (a cache in pieces): all of them or none -- on a refused piece
 // this request's pieces are given back and the state is 3.  The owner adopts them when the state says 2, none before
-static void frozen_alloc_pieces_in_thread(nk2d_frozen_cache* fc, int dev, size_t piece_bytes, size_t count, size_t piece_rows) {
+static void frozen_alloc_pieces_in_thread(nk2d_frozen_cache* fc, int dev, size_t piece_bytes, size_t count, size_t piece_rows, bool lean) {
     if (fc->alloc_thread.joinable()) fc->alloc_thread.join();
     fc->alloc_state.store(1);
     fc->alloc_is_pieces = true;
+    fc->alloc_lean = lean;
     fc->alloc_piece_rows = piece_rows;
     fc->alloc_pieces.clear();
     fc->alloc_thread = std::thread([fc, dev, piece_bytes, count]() {
@@ -642,9 +713,11 @@ static int frozen_adopt(nk2d_ctx* c, nk2d_frozen_cache* fc) {
         c->frozen_cache_piece_allocs += (int64_t)fc->alloc_pieces.size();
         fc->pieces.insert(fc->pieces.end(), fc->alloc_pieces.begin(), fc->alloc_pieces.end());
         fc->piece_rows = fc->alloc_piece_rows;
+        fc->lean = fc->alloc_lean;      // (pieces held before the request were of the same form: the other form goes first)
         fc->alloc_pieces.clear();
         return 0;
     }
+    fc->lean = fc->alloc_lean;
     fc->slab = fc->alloc_slab; fc->rows_dev = fc->alloc_rows; fc->frows_dev = fc->alloc_frows; fc->cap_rows = fc->alloc_cap;
     fc->alloc_slab = nullptr; fc->alloc_rows = nullptr; fc->alloc_frows = nullptr;
     fc->C.KV = nullptr;     // (the tables' places are set at the build)
@@ -669,13 +742,40 @@ static bool frozen_eligible(const nk2d_ctx* c, const double* sched, int64_t n) {
     return (int)sched[(n - 1) * NK2D_SCHED_WIDTH + 3] >= 1;
 }
 
+// The form of the cache of a schedule of `n` rows (option "frozen_cache_lean"; key_full: its key as a full cache).  0: full, 1: lean,
+// 2: lean only where the full cache would be refused -- by "frozen_cache_gb", or by the 85 % rule where it would have to be
+// allocated.  What a thread is allocating stays what it is, and so does a lean cache the 85 % rule chose for this very schedule
+// (the device is not asked again every year); "frozen_cache_gb" is looked at every time.
+static int frozen_form(nk2d_ctx* c, int64_t n, uint64_t key_full, bool* lean) {
+    *lean = c->frozen_cache_lean == 1;
+    if (c->frozen_cache_lean != 2) return 0;
+    const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
+    if (fc && fc->alloc_state.load() != 0) { *lean = fc->alloc_lean; return 0; }
+    const bool holds = fc && (fc->slab || !fc->pieces.empty());
+    const bool pieces = c->frozen_cache_pieces != 0;
+    const size_t B = pieces ? frozen_piece_rows(c, false) : 1, rows = ((size_t)n + B - 1) / B * B;
+    const double bytes = 8.0 * (double)rows * (double)frozen_row_doubles(c, false);
+    if (bytes > c->frozen_cache_max_gb * 1.0e9) { *lean = true; return 0; }
+    if (holds && !fc->lean) {       // (room enough in the full form already: nothing to allocate, nothing to refuse)
+        if (pieces ? (fc->piece_rows == B && fc->pieces.size() * B >= rows) : (fc->slab && fc->cap_rows >= (size_t)n)) return 0;
+    }
+    if (holds && fc->lean && fc->n == n && fc->key == (key_full ^ FROZEN_LEAN_KEY) && c->frozen_lean_mem_key == key_full) { *lean = true; return 0; }
+    size_t free_b = 0, total_b = 0;
+    NK2D_CHECK(c, hipMemGetInfo(&free_b, &total_b));
+    *lean = 1.02 * bytes > 0.85 * ((double)free_b + (double)nk2d_frozen_cache_bytes(c));
+    c->frozen_lean_mem_key = *lean ? key_full : 0;
+    return 0;
+}
+
 // Options "frozen_cache_pieces" + "frozen_cache_early": the pieces for the `n` rows of the schedule a free-running year just
 // recorded are asked for NOW, from the thread whatever their size, so that they are there when the first product comes; the
 // tables are built where they always are, at the first frozen year.  (With the slab this was measured and taken out, see
 // below; pieces are what makes the request one the driver can serve beside other allocations -- or not: DESIGN 3.6.)
 int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
     if (!c->frozen_cache_pieces || !c->frozen_cache_early || !sched || !frozen_eligible(c, sched, n)) return 0;
-    const size_t per_row = frozen_row_doubles(c), B = frozen_piece_rows(c), need = ((size_t)n + B - 1) / B;
+    bool want_lean = false;
+    NK2D_TRY(frozen_form(c, n, nk2d_frozen_key(c, sched, n), &want_lean));
+    const size_t per_row = frozen_row_doubles(c, want_lean), B = frozen_piece_rows(c, want_lean), need = ((size_t)n + B - 1) / B;
     const double bytes = 8.0 * (double)need * (double)B * (double)per_row;
     if (bytes > c->frozen_cache_max_gb * 1.0e9) return 0;
     nk2d_frozen_cache* fc = (nk2d_frozen_cache*)c->frozen_cache;
@@ -683,7 +783,7 @@ int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
     const int st = frozen_adopt(c, fc);
     if (st == 1) return 0;
     if (st == 3) { c->frozen_persistent = 0; return 0; }
-    if (fc->slab || (!fc->pieces.empty() && fc->piece_rows != B)) {
+    if (fc->slab || (!fc->pieces.empty() && (fc->piece_rows != B || fc->lean != want_lean))) {
         NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
         frozen_free_slab(fc);
         frozen_free_pieces(fc);
@@ -693,7 +793,7 @@ int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
     NK2D_CHECK(c, hipMemGetInfo(&free_b, &total_b));
     const double held = 8.0 * (double)fc->pieces.size() * (double)B * (double)per_row;
     if (1.02 * bytes > 0.85 * ((double)free_b + held)) return 0;
-    frozen_alloc_pieces_in_thread(fc, c->dev, sizeof(double) * B * per_row, need - fc->pieces.size(), B);
+    frozen_alloc_pieces_in_thread(fc, c->dev, sizeof(double) * B * per_row, need - fc->pieces.size(), B, want_lean);
     c->frozen_cache_early_requests++;
     return 0;
 }
@@ -709,9 +809,13 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     const size_t ntab = (size_t)c->ncol * NK2D_TAB * 64;
     // the cache as pieces (option "frozen_cache_pieces"): `need` pieces of `B` rows; the limits apply to their sum
     const bool want_pieces = c->frozen_cache_pieces != 0;
-    const size_t B = want_pieces ? frozen_piece_rows(c) : 0, need = want_pieces ? ((size_t)n + B - 1) / B : 0;
-    const double bytes = want_pieces ? 8.0 * (double)need * (double)B * (double)frozen_row_doubles(c)
-                                     : 8.0 * (double)n * (3.0 * c->kv_len + 5.0 * c->np + 3.0 * c->nv + 3.0 * ntab);
+    // lean (option "frozen_cache_lean"): rows of planes only; the limits apply to that size.  Its key is another
+    const uint64_t key_full = nk2d_frozen_key(c, sched, n);
+    bool want_lean = false;
+    NK2D_TRY(frozen_form(c, n, key_full, &want_lean));
+    const size_t per_row = frozen_row_doubles(c, want_lean);
+    const size_t B = want_pieces ? frozen_piece_rows(c, want_lean) : 0, need = want_pieces ? ((size_t)n + B - 1) / B : 0;
+    const double bytes = want_pieces ? 8.0 * (double)need * (double)B * (double)per_row : 8.0 * (double)n * (double)per_row;
     if (bytes > c->frozen_cache_max_gb * 1.0e9) return 1;
     {   // what a thread was asked for: not there yet (launch by launch), there (adopt it), or refused (never again)
         const int st = frozen_adopt(c, (nk2d_frozen_cache*)c->frozen_cache);
@@ -719,9 +823,10 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
         if (st == 3) { c->frozen_persistent = 0; return 1; }
     }
     if (nk2d_frozen_cache* have = (nk2d_frozen_cache*)c->frozen_cache) {
-        // a context never holds a slab and pieces at once: the other form (and pieces of another size) go first
-        const bool drop_slab = want_pieces && have->slab;
-        const bool drop_pieces = !have->pieces.empty() && (!want_pieces || have->piece_rows != B);
+        // a context never holds a slab and pieces at once, nor a full and a lean cache: the other form (and pieces of another
+        // size) go first
+        const bool drop_slab = have->slab && (want_pieces || have->lean != want_lean);
+        const bool drop_pieces = !have->pieces.empty() && (!want_pieces || have->piece_rows != B || have->lean != want_lean);
         if (drop_slab || drop_pieces) {
             NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
             if (drop_slab) frozen_free_slab(have);
@@ -735,20 +840,20 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             if (held_n < need) {
                 size_t free_b = 0, total_b = 0;
                 NK2D_CHECK(c, hipMemGetInfo(&free_b, &total_b));
-                const double held = 8.0 * (double)held_n * (double)B * (double)frozen_row_doubles(c);
+                const double held = 8.0 * (double)held_n * (double)B * (double)per_row;
                 if (1.02 * bytes > 0.85 * ((double)free_b + held)) return 1;
             }
         } else if (!have || have->cap_rows < (size_t)n) {
             size_t free_b = 0, total_b = 0;
             NK2D_CHECK(c, hipMemGetInfo(&free_b, &total_b));
-            const double held = have ? 8.0 * (double)have->cap_rows * (3.0 * c->kv_len + 5.0 * c->np + 3.0 * c->nv + 3.0 * ntab) : 0.0;
+            const double held = have ? 8.0 * (double)have->cap_rows * (double)per_row : 0.0;
             if (1.02 * bytes > 0.85 * ((double)free_b + held)) return 1;
         }
     }
     nk2d_frozen_cache* fc = (nk2d_frozen_cache*)c->frozen_cache;
     if (!fc) { fc = new nk2d_frozen_cache(); c->frozen_cache = fc; }
     // (the rows also say which steps carry an error estimate)
-    const uint64_t key = nk2d_frozen_key(c, sched, n);
+    const uint64_t key = key_full ^ (want_lean ? FROZEN_LEAN_KEY : 0);
     if (fc->key != key || fc->n != n) {
         // option "frozen_cache_after": that many years of a schedule run launch by launch before its cache is built.  Default
         // 0; -1: 0 for caches below 8 GB, 3 above.  Building a 100 GB cache takes 26 ms where a one-launch year saves 40
@@ -761,8 +866,15 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     DevP P = make_devp(c);
     if (fc->key != key || fc->n != n) {
         // ---- (re)build the cache for this schedule
+        if (want_lean && fc->lean_tab_doubles < 3 * c->nv + 3 * ntab) {
+            // the one row of factor tables the lean year's kernel works in: allocated once
+            NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+            if (fc->lean_tab) (void)hipFree(fc->lean_tab);
+            fc->lean_tab = nullptr; fc->lean_tab_doubles = 0;
+            NK2D_CHECK(c, hipMalloc((void**)&fc->lean_tab, sizeof(double) * (3 * c->nv + 3 * ntab)));
+            fc->lean_tab_doubles = 3 * c->nv + 3 * ntab;
+        }
         if (want_pieces) {
-            const size_t per_row = frozen_row_doubles(c);
             if (fc->pieces.size() < need) {
                 // more pieces, no headroom rows: what is there stays where it is
                 NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
@@ -770,7 +882,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
                 fc->key = 0; fc->n = 0;
                 if ((double)add * (double)piece_bytes > 8.0e9 && c->frozen_alloc_async) {
                     // (piece by piece from the thread: launch by launch until all of them are there)
-                    frozen_alloc_pieces_in_thread(fc, c->dev, piece_bytes, add, B);
+                    frozen_alloc_pieces_in_thread(fc, c->dev, piece_bytes, add, B, want_lean);
                     return 1;
                 }
                 const size_t before = fc->pieces.size();
@@ -785,6 +897,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
                     fc->pieces.push_back(p);
                 }
                 fc->piece_rows = B;
+                fc->lean = want_lean;
                 c->frozen_cache_piece_allocs += (int64_t)add;
             }
             if (fc->rows_cap < (size_t)n) {
@@ -809,7 +922,6 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             // ONE allocation for the whole cache, with room for the longer schedules of later Newton iterates: giving 100 GB
             // back and asking for them again costs seconds (measured inside a Newton run: 4.4 s), the first request 0.03 - 0.8 s
             NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
-            const size_t per_row = 3 * c->kv_len + 5 * c->np + 3 * c->nv + 3 * ntab;
             // (what this cache holds now is given back first -- by the thread, where a thread allocates)
             double* old_slab = fc->slab;
             CacheRow* old_rows = fc->rows_dev;
@@ -833,15 +945,19 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             }
             if (in_thread) {
                 // (the new slab and tables come from the thread: launch by launch until they are there)
-                frozen_alloc_in_thread(fc, c->dev, slab_bytes, cap, old_slab, old_rows, old_frows);
+                frozen_alloc_in_thread(fc, c->dev, slab_bytes, cap, old_slab, old_rows, old_frows, want_lean);
                 return 1;
             }
             NK2D_CHECK(c, hipMalloc((void**)&fc->slab, slab_bytes));
             NK2D_CHECK(c, hipMalloc((void**)&fc->rows_dev, sizeof(CacheRow) * cap));
             NK2D_CHECK(c, hipMalloc((void**)&fc->frows_dev, sizeof(FrozenRow) * cap));
             fc->cap_rows = cap;
+            fc->lean = want_lean;
         }
-        if (!want_pieces && (fc->C.KV != fc->slab || fc->C.nv != c->nv)) {   // (a new slab: the tables' places in it)
+        if (!want_pieces && want_lean) {
+            fc->C.KV = fc->slab;
+            fc->C.J = fc->slab + fc->cap_rows * 3 * c->kv_len;
+        } else if (!want_pieces && (fc->C.KV != fc->slab || fc->C.nv != c->nv || fc->C.fr_inv == fc->lean_tab)) {   // (a new slab: the tables' places in it)
             const size_t cap = fc->cap_rows;
             double* p = fc->slab;
             fc->C.KV = p; p += cap * 3 * c->kv_len;
@@ -851,6 +967,15 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             fc->C.fc_invi = p; p += cap * c->nv;
             fc->C.fr_tab = p; p += cap * ntab;
             fc->C.fc_tabr = p; p += cap * ntab;
+            fc->C.fc_tabi = p;
+        }
+        if (want_lean) {    // (slab or pieces: the six factor tables are the one row)
+            double* p = fc->lean_tab;
+            fc->C.fr_inv = p; p += c->nv;
+            fc->C.fc_invr = p; p += c->nv;
+            fc->C.fc_invi = p; p += c->nv;
+            fc->C.fr_tab = p; p += ntab;
+            fc->C.fc_tabr = p; p += ntab;
             fc->C.fc_tabi = p;
         }
         fc->C.kv_len = c->kv_len; fc->C.np = c->np; fc->C.nv = c->nv; fc->C.ntab = ntab;
@@ -880,6 +1005,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             if (c->min_sweeps > 1 && nk2d_has_lateral(c)) { m_real = std::max(m_real, 2); m_cplx = std::max(m_cplx, 2); }
             F.m = std::max(m_real, m_cplx);
             F.h = h;
+            F.cre = R.cre; F.ccr = R.ccr; F.cci = R.cci;
             // (single-sweep solves only: the estimate is then the column's own; two-sweep rows go unsampled)
             F.err = (c->frozen_err_check > 0 && i > 0 && i + 1 < n && (i % c->frozen_err_check) == 0 && F.m == 1 && F.n_iter >= 1) ? 1 : 0;
             F.x0 = F.x1 = F.x2 = 1.0;
@@ -901,21 +1027,27 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             NK2D_DISPATCH_E(c->E, hipLaunchKernelGGL((k_cache_planes<EE, 1>), dim3((unsigned)((tasks + 3) / 4)), dim3(NK2D_BLOCK), 0, nk2d_s(c),
                                                       P, fc->rows_dev, CP, (int)n));
             NK2D_CHECK(c, hipGetLastError());
-            const long long ftasks = 2LL * c->ncol * n;
-            NK2D_DISPATCH_EK(c->E, c->kind, hipLaunchKernelGGL((k_cache_factor<EE, KK, 1>), dim3((unsigned)((ftasks + 3) / 4)), dim3(NK2D_BLOCK), 0,
-                                                               nk2d_s(c), P, fc->rows_dev, CP, (int)n));
-            NK2D_CHECK(c, hipGetLastError());
-            c->st.nlaunch += 2;
+            c->st.nlaunch += 1;
+            if (!want_lean) {
+                const long long ftasks = 2LL * c->ncol * n;
+                NK2D_DISPATCH_EK(c->E, c->kind, hipLaunchKernelGGL((k_cache_factor<EE, KK, 1>), dim3((unsigned)((ftasks + 3) / 4)), dim3(NK2D_BLOCK), 0,
+                                                                   nk2d_s(c), P, fc->rows_dev, CP, (int)n));
+                NK2D_CHECK(c, hipGetLastError());
+                c->st.nlaunch += 1;
+            }
         } else {
             const long long tasks = 4LL * c->ny * n;
             NK2D_DISPATCH_E(c->E, hipLaunchKernelGGL(k_cache_planes<EE>, dim3((unsigned)((tasks + 3) / 4)), dim3(NK2D_BLOCK), 0, nk2d_s(c),
                                                       P, fc->rows_dev, fc->C, (int)n));
             NK2D_CHECK(c, hipGetLastError());
-            const long long ftasks = 2LL * c->ncol * n;
-            NK2D_DISPATCH_EK(c->E, c->kind, hipLaunchKernelGGL((k_cache_factor<EE, KK>), dim3((unsigned)((ftasks + 3) / 4)), dim3(NK2D_BLOCK), 0,
-                                                               nk2d_s(c), P, fc->rows_dev, fc->C, (int)n));
-            NK2D_CHECK(c, hipGetLastError());
-            c->st.nlaunch += 2;
+            c->st.nlaunch += 1;
+            if (!want_lean) {
+                const long long ftasks = 2LL * c->ncol * n;
+                NK2D_DISPATCH_EK(c->E, c->kind, hipLaunchKernelGGL((k_cache_factor<EE, KK>), dim3((unsigned)((ftasks + 3) / 4)), dim3(NK2D_BLOCK), 0,
+                                                                   nk2d_s(c), P, fc->rows_dev, fc->C, (int)n));
+                NK2D_CHECK(c, hipGetLastError());
+                c->st.nlaunch += 1;
+            }
         }
         fc->key = key;
         fc->n = n;
@@ -923,7 +1055,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     }
     // a cache in pieces: every piece that covers rows < n must be there -- the kernel never looks at a missing one
     if (want_pieces) {
-        if (fc->piece_rows != B || fc->pieces.size() < need || !fc->pieces_dev || fc->pieces_dev_cap < need) return 1;
+        if (fc->piece_rows != B || fc->lean != want_lean || fc->pieces.size() < need || !fc->pieces_dev || fc->pieces_dev_cap < need) return 1;
         for (size_t p = 0; p < need; ++p)
             if (!fc->pieces[p]) return 1;
     }
@@ -992,7 +1124,8 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             explicit Turn(int w) : waves(w) { nk2d_turn_take(waves); }
             ~Turn() { nk2d_turn_give(waves); }
         } turn(team ? 4 * c->ncol : c->ncol);
-        rc = want_pieces ? launch_frozen<1>(c, team, dim3(nblk), P, A) : launch_frozen<0>(c, team, dim3(nblk), P, static_cast<FrozenArgs&>(A));
+        if (want_lean) rc = want_pieces ? launch_frozen<1, 1>(c, team, dim3(nblk), P, A) : launch_frozen<0, 1>(c, team, dim3(nblk), P, static_cast<FrozenArgs&>(A));
+        else rc = want_pieces ? launch_frozen<1, 0>(c, team, dim3(nblk), P, A) : launch_frozen<0, 0>(c, team, dim3(nblk), P, static_cast<FrozenArgs&>(A));
         if (rc == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return 1; }
         NK2D_CHECK(c, rc);
         NK2D_CHECK(c, hipEventRecord(c->yr_ev[1], nk2d_s(c)));

@@ -1164,6 +1164,7 @@ int run_replay(Ctl& s, const double* sched, int64_t n, bool check) {
                 const int64_t bad_err = first_bad_err(sched, 0, -1, sampled);
                 if (bad_err >= 0) return err_failure(bad_err);
                 c->frozen_persistent_years++;
+                if (nk2d_frozen_cache_is_lean(c)) c->frozen_lean_years++;
                 return 0;
             }
             return 3;

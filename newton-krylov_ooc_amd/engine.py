@@ -220,6 +220,9 @@ class ModuleEngine:
             self.set_option("frozen_cache_piece_mb", float(os.environ["NK2D_FROZEN_CACHE_PIECE_MB"]))
         if "NK2D_FROZEN_CACHE_EARLY" in os.environ:
             self.set_option("frozen_cache_early", float(os.environ["NK2D_FROZEN_CACHE_EARLY"]))
+        # the schedule cache without the factor tables: 1 always, 2 where the full cache would be refused (csrc/nk2d_frozen.hip)
+        if "NK2D_FROZEN_CACHE_LEAN" in os.environ:
+            self.set_option("frozen_cache_lean", float(os.environ["NK2D_FROZEN_CACHE_LEAN"]))
         # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_TWO_ENDED" in os.environ:
             self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
