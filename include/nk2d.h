@@ -231,13 +231,23 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    the full rows, to which every limit above then applies -- and the year factorises in the first phase of every step, on one
    row's worth of factor tables; 1: every schedule cache of the context, 2: only a schedule whose full cache "frozen_cache_gb" or
    the 85 % rule would refuse; composes with pieces, switching lean <-> full frees the other form first, any other value is an
-   error, not taken with "factor_fp32").  Same device functions, bit-identical results; a year that does not pass the Newton check, or a
+   error, not taken with "factor_fp32"; "frozen_forced" (environment NK2D_FROZEN_FORCED), a bit mask, default 0, opt-in, read at
+   every frozen year: the one-launch year for the file-driven forced module (module_kind 2) where it has none by default -- bit 1:
+   without a sink threshold at five to eight levels per lane, on the full or the lean cache, slab or pieces; bit 2: WITH a sink
+   threshold (sink_thres > 0, whose Jacobian reads the state through one diagonal plane) at one to eight levels per lane, on the
+   lean cache only ("frozen_cache_lean" 1, or 2, which for such a context always means lean; with 0 the year routes as without
+   the option): a row of that cache also holds the file-source plane at its Jacobian time, 8 n (3 kv_len + 5 np + np) bytes, and
+   the year forms that diagonal plane for each wave's own column, from the state at the step start, at the rows where the
+   launch-per-phase path evaluates the Jacobian anew, in a plane the cache owns; any value outside 0 ... 3 is an error; phosphorus
+   contexts are unaffected).  Same device functions, bit-identical results; a year that does not pass the Newton check, or a
    barrier that times out, is handed to the launch-per-phase path.  Counters by name: "frozen_persistent_years",
    "frozen_team_years" (of them: a four-wave team per column), "frozen_cache_bytes",
    "frozen_launch_us" (device time of those launches), "frozen_cache_pending" (1 while a thread allocates a large cache or pieces),
    "frozen_cache_pieces" (pieces held; "frozen_cache_bytes" is then their sum), "frozen_cache_piece_allocs" (pieces allocated
    so far), "frozen_cache_early_requests" (early requests made), "frozen_cache_lean" (1 while the cache held is lean),
    "frozen_lean_years" (one-launch years run on a lean cache; also counted in "frozen_persistent_years"),
+   "frozen_forced_years" (one-launch years only option "frozen_forced" made possible; also counted in "frozen_persistent_years",
+   and in "frozen_lean_years" where lean),
    "frozen_cache_builds", "frozen_fallbacks", "frozen_resumes"; of the host-side controller: "spec_launches_dropped",
    "spec_front_launches_dropped", "err_estimates_queued", "err_estimates_dropped" (work queued ahead of a verdict); of the
    preconditioner (option "pc_two_ended"): "pc_setup_rounds" (dependent inversion rounds of the last block elimination: ny,

@@ -227,6 +227,13 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
         c->frozen_cache_lean = (int)value;
         return 0;
     }
+    if (key == "frozen_forced") {
+        // the one-launch year for the file-driven forced module where it has none by default (nk2d_frozen.hip).  Bit 1: linear sources at
+        // five to eight levels per lane; bit 2: a thresholded sink, on the lean cache.  Taken at the next frozen year
+        if (value != 0.0 && value != 1.0 && value != 2.0 && value != 3.0) return nk2d_fail(c, "nk2d_set_option: frozen_forced is a bit mask 0 ... 3");
+        c->frozen_forced = (int)value;
+        return 0;
+    }
     if (key == "frozen_cache_piece_mb") {
         if (!(value > 0.0) || !std::isfinite(value)) return nk2d_fail(c, "nk2d_set_option: frozen_cache_piece_mb must be > 0");
         c->frozen_cache_piece_mb = value;
@@ -604,6 +611,8 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_cache_lean = 0;
     c->frozen_lean_years = 0;
     c->frozen_lean_mem_key = 0;
+    c->frozen_forced = 0;
+    c->frozen_forced_years = 0;
     c->frozen_cache_piece_allocs = c->frozen_cache_early_requests = 0;
     c->frozen_coef_lds = 15;
     c->frozen_by_column = 1;
@@ -1149,6 +1158,7 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_cache_pieces") v = nk2d_frozen_cache_npieces(c);
     else if (key == "frozen_cache_lean") v = nk2d_frozen_cache_is_lean(c);
     else if (key == "frozen_lean_years") v = c->frozen_lean_years;
+    else if (key == "frozen_forced_years") v = c->frozen_forced_years;
     else if (key == "frozen_cache_piece_allocs") v = nk2d_frozen_cache_piece_allocs(c);
     else if (key == "frozen_cache_early_requests") v = c->frozen_cache_early_requests;
     else if (key == "frozen_fallbacks") v = c->frozen_fallbacks;

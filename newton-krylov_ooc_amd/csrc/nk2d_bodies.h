@@ -425,6 +425,24 @@ __device__ __forceinline__ void jac_cols(const DevP& P, const double (&kv)[E], i
     }
 }
 
+// forced module, file source with a sink threshold: column j of UPR = -d sms / d tracer at the linearisation state `ylin` and
+// the source plane `sms_plane` (forced.py:188-202).  The one place these expressions live: the Jacobian launch (jac_core) and the
+// one-launch frozen year of such a module (k_frozen_persistent, option "frozen_forced" bit 2) both call it.  MPY: how the state is loaded
+template <int E, int MPY = 0>
+__device__ __forceinline__ void forced_upr_col(const DevP& P, const double* __restrict__ ylin, const double* __restrict__ sms_plane,
+                                               double* __restrict__ UPR, int j, int lane) {
+    double cc[E], sms[E], upr[E];
+    load_col<E, MPY>(ylin, j, lane, cc);
+    load_col<E>(sms_plane, j, lane, sms);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const double tmp = P.f_thres_r * cc[e];
+        const bool on = P.f_thres_r != 0.0 && sms[e] < 0.0 && tmp > 0.0 && tmp < 1.0;
+        upr[e] = (on && (lane * E + e) < P.nz) ? -(P.f_thres_r * sms[e]) : 0.0;
+    }
+    store_col<E>(UPR, j, lane, upr);
+}
+
 // the same from a vertical mixing column held in registers (kvp: its bundle in memory, read only for the source plane of
 // a forced module with a thresholded sink)
 template <int E, int MP = 0>
@@ -443,16 +461,7 @@ __device__ __forceinline__ void jac_core(const DevP& P, const double (&kv)[E], c
     if (ylin != nullptr && P.f_sms > 0) {
         // forced module, file source with a sink threshold: UPR = -d sms / d tracer at the linearisation state
         // and the time of the bundle (forced.py:188-202); zero without a threshold
-        double cc[E], sms[E], upr[E];
-        load_col<E>(ylin, j, lane, cc);
-        load_col<E>(kvp + P.np, j, lane, sms);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const double tmp = P.f_thres_r * cc[e];
-            const bool on = P.f_thres_r != 0.0 && sms[e] < 0.0 && tmp > 0.0 && tmp < 1.0;
-            upr[e] = (on && (lane * E + e) < P.nz) ? -(P.f_thres_r * sms[e]) : 0.0;
-        }
-        store_col<E>(UPR, j, lane, upr);
+        forced_upr_col<E>(P, ylin, kvp + P.np, UPR, j, lane);
     } else if (ylin != nullptr) {
         // d uptake / d po4 at the linearisation state (phosphorus.py:97-103)
         double po4[E], light[E], upr[E];
@@ -2013,11 +2022,13 @@ struct PieceTab {
     double* const* base;                                // [pieces] on the device
     int rows;                                           // rows per piece
     size_t oJ, ofr, ofcr, ofci, otr, otcr, otci;        // where J, fr_inv, ... start inside a piece (KV starts it)
+    size_t oS;                                          // ... and the file-source planes of a thresholded forced module (lean; else 0)
 };
 
 // the tables of ONE row
 struct RowTabs {
     double *KV, *J, *fr_inv, *fc_invr, *fc_invi, *fr_tab, *fc_tabr, *fc_tabi;
+    double* SRC;         // the file-source plane at the row's Jacobian time (PieceTab::oS; meaningful with option "frozen_forced" bit 2 only)
 };
 
 // a pointer every lane holds identically, into scalar registers
@@ -2039,6 +2050,7 @@ __device__ __forceinline__ RowTabs piece_row_tabs(const CachePtrs& C, const Piec
     t.fr_tab = b + T.otr + (size_t)r * C.ntab;
     t.fc_tabr = b + T.otcr + (size_t)r * C.ntab;
     t.fc_tabi = b + T.otci + (size_t)r * C.ntab;
+    t.SRC = b + T.oS + (size_t)r * C.np;
     return t;
 }
 
@@ -2199,6 +2211,7 @@ struct FrozenRow {
     int n_iter, m;               // simplified-Newton iterations, sweeps per solve
     double h;                    // step size
     int err;                     // 1: SciPy's error estimate of this step is evaluated too (its partials to row 3 i + 2 of STEP_PART)
+    int upr;                     // 1: the row takes a new Jacobian (t_jac differs from the row before): a thresholded forced module forms UPR anew
     double cre, ccr, cci;        // shifts of the row's line factorisation (h_lu): what the LEAN year factorises with in the row's first phase
 };
 
@@ -2217,6 +2230,10 @@ struct FrozenArgs {
     int fences;
     int coef_lds;                // option "frozen_coef_lds" (bits of LdsSrc): what a wave finds in LDS; bits 2, 3 need `by_column`
     int by_column;               // 1: a workgroup is ONE ypos column with all its tracers (a wave each) instead of adjacent columns of one tracer
+    // option "frozen_forced" bit 2 (forced module with a thresholded sink, lean cache): the rows' file-source planes at their Jacobian
+    // times, [n][np] behind J in the slab (a cache in pieces: PieceTab::oS), and 1 where the year forms UPR from them
+    const double* SRC;
+    int upr_on;
 };
 
 // the arguments of the piece flavour of k_frozen_persistent: those of the slab flavour (the table pointers of C unused, its

@@ -148,6 +148,9 @@ struct nk2d_ctx {
     int frozen_cache_lean;            // 0 (default): the full cache, 1: lean, 2: lean where the full cache would be refused
     int64_t frozen_lean_years;        // lean one-launch years run (also counted in frozen_persistent_years)
     uint64_t frozen_lean_mem_key;     // mode 2: the schedule whose full cache the 85 % rule refused last
+    // option "frozen_forced": the one-launch year for the file-driven forced module (kind 2) where it has none by default
+    int frozen_forced;                // bit mask, default 0.  1: linear sources at five to eight levels per lane; 2: a thresholded sink (lean cache only)
+    int64_t frozen_forced_years;      // one-launch years only that option made possible (also counted in frozen_persistent_years)
     int frozen_cache_early;           // option "frozen_cache_early": with pieces, the year that records a schedule asks for its pieces when it ends
     int64_t frozen_cache_piece_allocs, frozen_cache_early_requests;   // counters: pieces allocated so far, early requests made
     uint64_t frozen_seen_key; int frozen_seen_years;   // the schedule last seen by nk2d_frozen_persistent and its years so far

@@ -37,6 +37,19 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_cache_planes(DevP P, const Cache
         store_col<E>(J + 2 * np, j, lane, so);
         store_col<E>(J + 3 * np, j, lane, no);
         store_col<E>(J + 4 * np, j, lane, ce);
+        if (R.v.out[3] != nullptr && P.f_sms > 0) {
+            // a forced module with a thresholded sink (option "frozen_forced" bit 2): the file source at the row's Jacobian time,
+            // vmix_body_kv's expressions with slot 3's records -- what the year forms UPR from
+            double lo[E], hi[E], val[E];
+            load_col<E>(P.SMSREC + (size_t)R.v.srec[3] * P.np, j, lane, lo);
+            load_col<E>(P.SMSREC + (size_t)(R.v.srec[3] + 1) * P.np, j, lane, hi);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const double slope = (hi[e] - lo[e]) / R.v.sden[3];
+                val[e] = ((lane * E + e) < P.nz) ? slope * R.v.sdx[3] + lo[e] : 0.0;
+            }
+            store_col<E>(R.v.out[3], j, lane, val);
+        }
     }
 }
 
@@ -216,6 +229,18 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typena
         }
         const double* kvb = PIECES ? T.KV : A.C.KV + (size_t)i * 3 * A.C.kv_len;
         const double* J = PIECES ? T.J : A.C.J + (size_t)i * 5 * A.C.np;
+        if constexpr (KIND == 2 && LEAN) {
+            // a thresholded sink (option "frozen_forced" bit 2): UPR = -d sms / d c of the wave's own column, at the rows where the
+            // launch path evaluates the Jacobian anew, from the state at the step start (its own y_new of the row before, or the
+            // year's input) and the file source at the row's Jacobian time -- jac_core's expressions, into the plane P.UPR names
+            // (the cache's own).  The row's phases read it through line_diag_from: the wave's own stores, read back by itself
+            // (every wave of a team forms the column for itself: the same values to the same places)
+            if (A.upr_on != 0 && uni_i(R.upr) != 0 && col_wave) {
+                const double* sp = PIECES ? T.SRC : A.SRC + (size_t)i * A.C.np;
+                forced_upr_col<E, MPX>(P, FZ_Y, sp, const_cast<double*>(P.UPR), wave % P.ny, lane);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
         // SciPy's error estimate on this step too (every "frozen_err_check"-th: the host compares it with what the recorded
         // step was accepted with).  Three phases of their own, one wave per column: the tendency at the step start before the
         // Newton iterations, the estimate behind the last of them -- which is then an ordinary iteration --, the end of the step
@@ -448,18 +473,28 @@ struct nk2d_frozen_cache {
     bool alloc_lean = false;            // the form a thread's allocation was asked for
     double* lean_tab = nullptr;
     size_t lean_tab_doubles = 0;
+    // option "frozen_forced" bit 2 (a forced module with a thresholded sink; lean only): every row also holds the file-source plane at
+    // its Jacobian time (np doubles, behind J), and `upr` is the plane the year's kernel forms UPR in (nv doubles, allocated once):
+    // the context's own UPR stays what the launch path left there
+    bool src = false;
+    bool alloc_src = false;
+    double* upr = nullptr;
+    size_t upr_doubles = 0;
 };
 
-// doubles of a row of the cache (lean: the planes only)
-static size_t frozen_row_doubles(const nk2d_ctx* c, bool lean) {
+// a forced module whose file source has a sink threshold: its Jacobian reads the state (the diagonal plane UPR)
+static bool frozen_thres(const nk2d_ctx* c) { return c->kind == 2 && c->d.sms_nrec > 0 && c->d.sink_thres > 0.0; }
+
+// doubles of a row of the cache (lean: the planes only; src: and the file-source plane at the Jacobian time)
+static size_t frozen_row_doubles(const nk2d_ctx* c, bool lean, bool src) {
     const size_t ntab = (size_t)c->ncol * NK2D_TAB * 64;
-    return 3 * c->kv_len + 5 * c->np + (lean ? 0 : 3 * c->nv + 3 * ntab);
+    return 3 * c->kv_len + 5 * c->np + (lean ? 0 : 3 * c->nv + 3 * ntab) + (src ? c->np : 0);
 }
 
 // rows per piece: option "frozen_cache_piece_rows", or what fits "frozen_cache_piece_mb" MiB (at least one)
-static size_t frozen_piece_rows(const nk2d_ctx* c, bool lean) {
+static size_t frozen_piece_rows(const nk2d_ctx* c, bool lean, bool src) {
     if (c->frozen_cache_piece_rows > 0) return (size_t)c->frozen_cache_piece_rows;
-    const double fit = std::floor(c->frozen_cache_piece_mb * 1048576.0 / (8.0 * (double)frozen_row_doubles(c, lean)));
+    const double fit = std::floor(c->frozen_cache_piece_mb * 1048576.0 / (8.0 * (double)frozen_row_doubles(c, lean, src)));
     return fit >= 1.0 ? (size_t)std::min(fit, 1.0e9) : (size_t)1;
 }
 
@@ -497,8 +532,10 @@ static uint64_t sched_key(const double* sched, int64_t n) {
 
 // what a schedule cache (and a command tape, option "frozen_tape") is kept for: the schedule, the context's fingerprint and the
 // error-estimate stride
-// (a LEAN cache of the same schedule has another key: a full cache is never read as a lean one)
+// (a LEAN cache of the same schedule has another key: a full cache is never read as a lean one; so has a lean cache with the
+// file-source planes of option "frozen_forced" bit 2)
 static const uint64_t FROZEN_LEAN_KEY = 0xC2B2AE3D27D4EB4Full;
+static const uint64_t FROZEN_SRC_KEY = 0x165667B19E3779F9ull;
 uint64_t nk2d_frozen_key(const nk2d_ctx* c, const double* sched, int64_t n) {
     return sched_key(sched, n) ^ (uint64_t)nk2d_fingerprint(c) ^ ((uint64_t)(c->frozen_err_check + 1) * 0x9E3779B97F4A7C15ull);
 }
@@ -510,8 +547,10 @@ static PieceTab frozen_piece_tab(const nk2d_ctx* c, const nk2d_frozen_cache* fc)
     T.base = fc->pieces_dev;
     T.rows = (int)B;
     T.oJ = B * 3 * c->kv_len;
-    if (fc->lean) {     // (a piece ends behind J: the offsets of the absent tables are unused)
+    T.oS = 0;
+    if (fc->lean) {     // (a piece ends behind J, or behind the source planes: the offsets of the absent tables are unused)
         T.ofr = T.ofcr = T.ofci = T.otr = T.otcr = T.otci = 0;
+        if (fc->src) T.oS = T.oJ + B * 5 * c->np;
         return T;
     }
     T.ofr = T.oJ + B * 5 * c->np;
@@ -533,9 +572,9 @@ int nk2d_frozen_cache_pending(const nk2d_ctx* c) {
 int64_t nk2d_frozen_cache_bytes(const nk2d_ctx* c) {
     const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
     if (!fc) return 0;
-    if (!fc->pieces.empty()) return (int64_t)(8 * fc->pieces.size() * fc->piece_rows * frozen_row_doubles(c, fc->lean));
+    if (!fc->pieces.empty()) return (int64_t)(8 * fc->pieces.size() * fc->piece_rows * frozen_row_doubles(c, fc->lean, fc->src));
     if (!fc->slab) return 0;
-    return (int64_t)(8 * fc->cap_rows * frozen_row_doubles(c, fc->lean));
+    return (int64_t)(8 * fc->cap_rows * frozen_row_doubles(c, fc->lean, fc->src));
 }
 
 // 1 while the schedule cache this context holds is lean (option "frozen_cache_lean")
@@ -571,6 +610,7 @@ void nk2d_frozen_cache_free(nk2d_ctx* c) {
     frozen_free_pieces(fc);
     frozen_free_slab(fc);
     if (fc->lean_tab) (void)hipFree(fc->lean_tab);
+    if (fc->upr) (void)hipFree(fc->upr);
     delete fc;
     c->frozen_cache = nullptr;
 }
@@ -632,11 +672,12 @@ static hipError_t launch_frozen_e(nk2d_ctx* c, dim3 grid, DevP& P, typename Froz
         // three and four levels per lane: a wave per column (all module kinds)
         case 3: if constexpr (!TEAM) return launch_frozen_one<3, KIND, 0, PIECES, LEAN>(c, grid, P, A); else break;
         case 4: if constexpr (!TEAM) return launch_frozen_one<4, KIND, 0, PIECES, LEAN>(c, grid, P, A); else break;
-        // five to eight levels per lane (up to 512 levels): a wave per column, linear sources
-        case 5: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<5, 0, 0, PIECES, LEAN>(c, grid, P, A); else break;
-        case 6: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<6, 0, 0, PIECES, LEAN>(c, grid, P, A); else break;
-        case 7: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<7, 0, 0, PIECES, LEAN>(c, grid, P, A); else break;
-        case 8: if constexpr (!TEAM && KIND == 0) return launch_frozen_one<8, 0, 0, PIECES, LEAN>(c, grid, P, A); else break;
+        // five to eight levels per lane (up to 512 levels): a wave per column; linear sources, and the file-driven forced module
+        // (option "frozen_forced": frozen_eligible() lets it come here)
+        case 5: if constexpr (!TEAM) return launch_frozen_one<5, KIND, 0, PIECES, LEAN>(c, grid, P, A); else break;
+        case 6: if constexpr (!TEAM) return launch_frozen_one<6, KIND, 0, PIECES, LEAN>(c, grid, P, A); else break;
+        case 7: if constexpr (!TEAM) return launch_frozen_one<7, KIND, 0, PIECES, LEAN>(c, grid, P, A); else break;
+        case 8: if constexpr (!TEAM) return launch_frozen_one<8, KIND, 0, PIECES, LEAN>(c, grid, P, A); else break;
         default: break;
     }
     return hipErrorInvalidValue;
@@ -651,11 +692,12 @@ static hipError_t launch_frozen(nk2d_ctx* c, bool team, dim3 grid, DevP& P, type
 // the slab of a schedule cache with room for `cap` rows from a thread of the library's own (hipMalloc of 120 GB: 0.03 - 3 s);
 // what the cache held before is given back by that thread first.  alloc_state 1 while it runs, 2 / 3 when done / refused
 static void frozen_alloc_in_thread(nk2d_frozen_cache* fc, int dev, size_t slab_bytes, size_t cap, double* old_slab, CacheRow* old_rows,
-                                   FrozenRow* old_frows, bool lean) {
+                                   FrozenRow* old_frows, bool lean, bool src) {
     if (fc->alloc_thread.joinable()) fc->alloc_thread.join();
     fc->alloc_state.store(1);
     fc->alloc_is_pieces = false;
     fc->alloc_lean = lean;
+    fc->alloc_src = src;
     fc->alloc_thread = std::thread([fc, dev, slab_bytes, cap, old_slab, old_rows, old_frows]() {
         bool ok = hipSetDevice(dev) == hipSuccess;
         if (old_slab) (void)hipFree(old_slab);
@@ -678,11 +720,12 @@ static void frozen_alloc_in_thread(nk2d_frozen_cache* fc, int dev, size_t slab_b
 
 // `count` more pieces of `piece_bytes` each from that thread (a cache in pieces): all of them or none -- on a refused piece
 // this request's pieces are given back and the state is 3.  The owner adopts them when the state says 2, none before
-static void frozen_alloc_pieces_in_thread(nk2d_frozen_cache* fc, int dev, size_t piece_bytes, size_t count, size_t piece_rows, bool lean) {
+static void frozen_alloc_pieces_in_thread(nk2d_frozen_cache* fc, int dev, size_t piece_bytes, size_t count, size_t piece_rows, bool lean, bool src) {
     if (fc->alloc_thread.joinable()) fc->alloc_thread.join();
     fc->alloc_state.store(1);
     fc->alloc_is_pieces = true;
     fc->alloc_lean = lean;
+    fc->alloc_src = src;
     fc->alloc_piece_rows = piece_rows;
     fc->alloc_pieces.clear();
     fc->alloc_thread = std::thread([fc, dev, piece_bytes, count]() {
@@ -714,10 +757,12 @@ static int frozen_adopt(nk2d_ctx* c, nk2d_frozen_cache* fc) {
         fc->pieces.insert(fc->pieces.end(), fc->alloc_pieces.begin(), fc->alloc_pieces.end());
         fc->piece_rows = fc->alloc_piece_rows;
         fc->lean = fc->alloc_lean;      // (pieces held before the request were of the same form: the other form goes first)
+        fc->src = fc->alloc_src;
         fc->alloc_pieces.clear();
         return 0;
     }
     fc->lean = fc->alloc_lean;
+    fc->src = fc->alloc_src;
     fc->slab = fc->alloc_slab; fc->rows_dev = fc->alloc_rows; fc->frows_dev = fc->alloc_frows; fc->cap_rows = fc->alloc_cap;
     fc->alloc_slab = nullptr; fc->alloc_rows = nullptr; fc->alloc_frows = nullptr;
     fc->C.KV = nullptr;     // (the tables' places are set at the build)
@@ -726,13 +771,34 @@ static int frozen_adopt(nk2d_ctx* c, nk2d_frozen_cache* fc) {
 
 // is the one-launch year made for this context and schedule?
 static bool frozen_eligible(const nk2d_ctx* c, const double* sched, int64_t n) {
-    const bool needs_state = c->kind == 1 || (c->kind == 2 && c->d.sms_nrec > 0 && c->d.sink_thres > 0.0);
+    // a Jacobian that reads the state: never for phosphorus; a forced module with a thresholded sink with option "frozen_forced" bit 2,
+    // on the lean cache only (its full cache -- factorisations ahead of the state -- cannot exist)
+    const bool thres = frozen_thres(c);
+    const bool needs_state = c->kind == 1 || (thres && !((c->frozen_forced & 2) && c->frozen_cache_lean != 0));
     if (!c->frozen_persistent || needs_state || c->hist_n != 0 || c->norm_hook || n < 1) return false;
     // the cache holds the factorisation in double precision only: with option "factor_fp32" the recorded year read the single
     // precision copies, and the one-launch year would not be the same discrete map (round-3 ADVICE) -- launch by launch then
     if (c->factor_fp32) return false;
-    // (instantiated for one to four levels per lane, and for five to eight with linear sources)
-    if (c->E > c->frozen_persistent_max_e || c->E > 8 || (c->E > 4 && c->kind != 0)) return false;
+    // (one to four levels per lane; five to eight with linear sources -- for the file-driven forced module there with option
+    // "frozen_forced": bit 1 without, bit 2 with a sink threshold)
+    if (c->E > c->frozen_persistent_max_e || c->E > 8) return false;
+    if (c->E > 4 && c->kind != 0 && !(c->kind == 2 && (c->frozen_forced & (thres ? 2 : 1)))) return false;
+    if (thres) {
+        // UPR is formed where the launch path evaluates the Jacobian anew (replay_rows): at a step start, or -- option
+        // "jac_stage_state" -- at a stage time of the row's own attempt.  A schedule it would refuse goes to it, to be refused
+        const double RCs[3] = {0.15505102572168222, 0.6449489742783178, 1.0};
+        double t_jac_prev = c->d.t0;
+        for (int64_t i = 0; i < n; ++i) {
+            const double* r = sched + i * NK2D_SCHED_WIDTH;
+            const double t = r[0], h = r[2], t_jac = r[4];
+            if (t_jac != t_jac_prev && t_jac != t) {
+                bool at_stage = false;
+                for (int k = 0; k < 3 && c->jac_stage_state; ++k) at_stage = at_stage || t_jac == t + (h * RCs[k]);
+                if (!at_stage) return false;
+            }
+            t_jac_prev = t_jac;
+        }
+    }
     // every row but the last must hand over to the next one (t_new == next t, whole step taken): the step-ending launch
     // predicts the next attempt from this step's collocation polynomial
     for (int64_t i = 0; i + 1 < n; ++i) {
@@ -748,13 +814,14 @@ static bool frozen_eligible(const nk2d_ctx* c, const double* sched, int64_t n) {
 // (the device is not asked again every year); "frozen_cache_gb" is looked at every time.
 static int frozen_form(nk2d_ctx* c, int64_t n, uint64_t key_full, bool* lean) {
     *lean = c->frozen_cache_lean == 1;
+    if (frozen_thres(c)) { *lean = true; return 0; }    // (eligible with a lean cache only: "frozen_cache_lean" 2 always means lean here)
     if (c->frozen_cache_lean != 2) return 0;
     const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
     if (fc && fc->alloc_state.load() != 0) { *lean = fc->alloc_lean; return 0; }
     const bool holds = fc && (fc->slab || !fc->pieces.empty());
     const bool pieces = c->frozen_cache_pieces != 0;
-    const size_t B = pieces ? frozen_piece_rows(c, false) : 1, rows = ((size_t)n + B - 1) / B * B;
-    const double bytes = 8.0 * (double)rows * (double)frozen_row_doubles(c, false);
+    const size_t B = pieces ? frozen_piece_rows(c, false, false) : 1, rows = ((size_t)n + B - 1) / B * B;
+    const double bytes = 8.0 * (double)rows * (double)frozen_row_doubles(c, false, false);
     if (bytes > c->frozen_cache_max_gb * 1.0e9) { *lean = true; return 0; }
     if (holds && !fc->lean) {       // (room enough in the full form already: nothing to allocate, nothing to refuse)
         if (pieces ? (fc->piece_rows == B && fc->pieces.size() * B >= rows) : (fc->slab && fc->cap_rows >= (size_t)n)) return 0;
@@ -775,7 +842,8 @@ int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
     if (!c->frozen_cache_pieces || !c->frozen_cache_early || !sched || !frozen_eligible(c, sched, n)) return 0;
     bool want_lean = false;
     NK2D_TRY(frozen_form(c, n, nk2d_frozen_key(c, sched, n), &want_lean));
-    const size_t per_row = frozen_row_doubles(c, want_lean), B = frozen_piece_rows(c, want_lean), need = ((size_t)n + B - 1) / B;
+    const bool want_src = frozen_thres(c);
+    const size_t per_row = frozen_row_doubles(c, want_lean, want_src), B = frozen_piece_rows(c, want_lean, want_src), need = ((size_t)n + B - 1) / B;
     const double bytes = 8.0 * (double)need * (double)B * (double)per_row;
     if (bytes > c->frozen_cache_max_gb * 1.0e9) return 0;
     nk2d_frozen_cache* fc = (nk2d_frozen_cache*)c->frozen_cache;
@@ -783,7 +851,7 @@ int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
     const int st = frozen_adopt(c, fc);
     if (st == 1) return 0;
     if (st == 3) { c->frozen_persistent = 0; return 0; }
-    if (fc->slab || (!fc->pieces.empty() && (fc->piece_rows != B || fc->lean != want_lean))) {
+    if (fc->slab || (!fc->pieces.empty() && (fc->piece_rows != B || fc->lean != want_lean || fc->src != want_src))) {
         NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
         frozen_free_slab(fc);
         frozen_free_pieces(fc);
@@ -793,7 +861,7 @@ int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
     NK2D_CHECK(c, hipMemGetInfo(&free_b, &total_b));
     const double held = 8.0 * (double)fc->pieces.size() * (double)B * (double)per_row;
     if (1.02 * bytes > 0.85 * ((double)free_b + held)) return 0;
-    frozen_alloc_pieces_in_thread(fc, c->dev, sizeof(double) * B * per_row, need - fc->pieces.size(), B, want_lean);
+    frozen_alloc_pieces_in_thread(fc, c->dev, sizeof(double) * B * per_row, need - fc->pieces.size(), B, want_lean, want_src);
     c->frozen_cache_early_requests++;
     return 0;
 }
@@ -813,8 +881,10 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     const uint64_t key_full = nk2d_frozen_key(c, sched, n);
     bool want_lean = false;
     NK2D_TRY(frozen_form(c, n, key_full, &want_lean));
-    const size_t per_row = frozen_row_doubles(c, want_lean);
-    const size_t B = want_pieces ? frozen_piece_rows(c, want_lean) : 0, need = want_pieces ? ((size_t)n + B - 1) / B : 0;
+    // (a thresholded forced module -- eligible with option "frozen_forced" bit 2 only, and lean: a row holds its source plane too)
+    const bool want_src = frozen_thres(c);
+    const size_t per_row = frozen_row_doubles(c, want_lean, want_src);
+    const size_t B = want_pieces ? frozen_piece_rows(c, want_lean, want_src) : 0, need = want_pieces ? ((size_t)n + B - 1) / B : 0;
     const double bytes = want_pieces ? 8.0 * (double)need * (double)B * (double)per_row : 8.0 * (double)n * (double)per_row;
     if (bytes > c->frozen_cache_max_gb * 1.0e9) return 1;
     {   // what a thread was asked for: not there yet (launch by launch), there (adopt it), or refused (never again)
@@ -825,8 +895,9 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     if (nk2d_frozen_cache* have = (nk2d_frozen_cache*)c->frozen_cache) {
         // a context never holds a slab and pieces at once, nor a full and a lean cache: the other form (and pieces of another
         // size) go first
-        const bool drop_slab = have->slab && (want_pieces || have->lean != want_lean);
-        const bool drop_pieces = !have->pieces.empty() && (!want_pieces || have->piece_rows != B || have->lean != want_lean);
+        const bool other_form = have->lean != want_lean || have->src != want_src;
+        const bool drop_slab = have->slab && (want_pieces || other_form);
+        const bool drop_pieces = !have->pieces.empty() && (!want_pieces || have->piece_rows != B || other_form);
         if (drop_slab || drop_pieces) {
             NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
             if (drop_slab) frozen_free_slab(have);
@@ -853,7 +924,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     nk2d_frozen_cache* fc = (nk2d_frozen_cache*)c->frozen_cache;
     if (!fc) { fc = new nk2d_frozen_cache(); c->frozen_cache = fc; }
     // (the rows also say which steps carry an error estimate)
-    const uint64_t key = key_full ^ (want_lean ? FROZEN_LEAN_KEY : 0);
+    const uint64_t key = key_full ^ (want_lean ? FROZEN_LEAN_KEY : 0) ^ (want_src ? FROZEN_SRC_KEY : 0);
     if (fc->key != key || fc->n != n) {
         // option "frozen_cache_after": that many years of a schedule run launch by launch before its cache is built.  Default
         // 0; -1: 0 for caches below 8 GB, 3 above.  Building a 100 GB cache takes 26 ms where a one-launch year saves 40
@@ -874,6 +945,14 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             NK2D_CHECK(c, hipMalloc((void**)&fc->lean_tab, sizeof(double) * (3 * c->nv + 3 * ntab)));
             fc->lean_tab_doubles = 3 * c->nv + 3 * ntab;
         }
+        if (want_src && fc->upr_doubles < c->nv) {
+            // the plane the year's kernel forms UPR in: allocated once
+            NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
+            if (fc->upr) (void)hipFree(fc->upr);
+            fc->upr = nullptr; fc->upr_doubles = 0;
+            NK2D_CHECK(c, hipMalloc((void**)&fc->upr, sizeof(double) * c->nv));
+            fc->upr_doubles = c->nv;
+        }
         if (want_pieces) {
             if (fc->pieces.size() < need) {
                 // more pieces, no headroom rows: what is there stays where it is
@@ -882,7 +961,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
                 fc->key = 0; fc->n = 0;
                 if ((double)add * (double)piece_bytes > 8.0e9 && c->frozen_alloc_async) {
                     // (piece by piece from the thread: launch by launch until all of them are there)
-                    frozen_alloc_pieces_in_thread(fc, c->dev, piece_bytes, add, B, want_lean);
+                    frozen_alloc_pieces_in_thread(fc, c->dev, piece_bytes, add, B, want_lean, want_src);
                     return 1;
                 }
                 const size_t before = fc->pieces.size();
@@ -898,6 +977,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
                 }
                 fc->piece_rows = B;
                 fc->lean = want_lean;
+                fc->src = want_src;
                 c->frozen_cache_piece_allocs += (int64_t)add;
             }
             if (fc->rows_cap < (size_t)n) {
@@ -945,7 +1025,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             }
             if (in_thread) {
                 // (the new slab and tables come from the thread: launch by launch until they are there)
-                frozen_alloc_in_thread(fc, c->dev, slab_bytes, cap, old_slab, old_rows, old_frows, want_lean);
+                frozen_alloc_in_thread(fc, c->dev, slab_bytes, cap, old_slab, old_rows, old_frows, want_lean, want_src);
                 return 1;
             }
             NK2D_CHECK(c, hipMalloc((void**)&fc->slab, slab_bytes));
@@ -953,6 +1033,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             NK2D_CHECK(c, hipMalloc((void**)&fc->frows_dev, sizeof(FrozenRow) * cap));
             fc->cap_rows = cap;
             fc->lean = want_lean;
+            fc->src = want_src;
         }
         if (!want_pieces && want_lean) {
             fc->C.KV = fc->slab;
@@ -995,7 +1076,10 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
                 if (want_pieces) R.v.out[k] = (k < 3) ? fc->pieces[(size_t)i / B] + (((size_t)i % B) * 3 + k) * c->kv_len : nullptr;
                 else R.v.out[k] = (k < 3) ? fc->C.KV + ((size_t)i * 3 + k) * c->kv_len : nullptr;
             }
-            vmix_forcing_args(c, 3, times, R.v);
+            // (slot 3 of a thresholded forced module: where the file source at the Jacobian time goes, behind the J planes)
+            if (want_src) R.v.out[3] = want_pieces ? fc->pieces[(size_t)i / B] + B * (3 * c->kv_len + 5 * c->np) + ((size_t)i % B) * c->np
+                                                   : fc->C.J + fc->cap_rows * 5 * c->np + (size_t)i * c->np;
+            vmix_forcing_args(c, want_src ? 4 : 3, times, R.v);
             R.v.bldmin = c->d.bldepth_min; R.v.y0 = c->d.vmix_log_shallow; R.v.y1 = c->d.vmix_log_deep; R.v.hw = c->d.vmix_half_width;
             R.cre = MU_REAL / h_lu; R.ccr = MU_CR / h_lu; R.cci = MU_CI / h_lu;
             FrozenRow& F = fc->frows[(size_t)i];
@@ -1008,6 +1092,8 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             F.cre = R.cre; F.ccr = R.ccr; F.cci = R.cci;
             // (single-sweep solves only: the estimate is then the column's own; two-sweep rows go unsampled)
             F.err = (c->frozen_err_check > 0 && i > 0 && i + 1 < n && (i % c->frozen_err_check) == 0 && F.m == 1 && F.n_iter >= 1) ? 1 : 0;
+            // (the launch path evaluates the Jacobian where t_jac changes -- replay_rows; the year's first row: from the state it starts at)
+            F.upr = (i == 0 || t_jac != sched[(i - 1) * NK2D_SCHED_WIDTH + 4]) ? 1 : 0;
             F.x0 = F.x1 = F.x2 = 1.0;
             if (i + 1 < n) {
                 const double h2 = r[NK2D_SCHED_WIDTH + 2];
@@ -1055,7 +1141,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     }
     // a cache in pieces: every piece that covers rows < n must be there -- the kernel never looks at a missing one
     if (want_pieces) {
-        if (fc->piece_rows != B || fc->lean != want_lean || fc->pieces.size() < need || !fc->pieces_dev || fc->pieces_dev_cap < need) return 1;
+        if (fc->piece_rows != B || fc->lean != want_lean || fc->src != want_src || fc->pieces.size() < need || !fc->pieces_dev || fc->pieces_dev_cap < need) return 1;
         for (size_t p = 0; p < need; ++p)
             if (!fc->pieces[p]) return 1;
     }
@@ -1087,6 +1173,10 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     A.out = c->YR_OUT;
     A.spin_ticks = (long long)(c->barrier_timeout_ms * 1.0e5);
     A.fences = c->year_fences;
+    // a thresholded forced module: the year forms UPR, in the cache's own plane, from the rows' source planes
+    A.upr_on = want_src ? 1 : 0;
+    A.SRC = (want_src && !want_pieces) ? fc->C.J + fc->cap_rows * 5 * c->np : nullptr;
+    if (want_src) P.UPR = fc->upr;
     // what lives in LDS (option "frozen_coef_lds", bits of LdsSrc) and which columns share a workgroup (option "frozen_by_column"):
     // as much as lets a compute unit hold what the grid needs of it -- ceil(waves / compute units) waves: pivots, then the step
     // block, then W are given up until it fits the 160 KB (E = 8 keeps everything but the pivots)

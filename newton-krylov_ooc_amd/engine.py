@@ -223,6 +223,10 @@ class ModuleEngine:
         # the schedule cache without the factor tables: 1 always, 2 where the full cache would be refused (csrc/nk2d_frozen.hip)
         if "NK2D_FROZEN_CACHE_LEAN" in os.environ:
             self.set_option("frozen_cache_lean", float(os.environ["NK2D_FROZEN_CACHE_LEAN"]))
+        # the one-launch frozen year for the file-driven forced module where it has none by default: bit 1 linear sources at five to
+        # eight levels per lane, bit 2 a thresholded sink on the lean cache (csrc/nk2d_frozen.hip)
+        if "NK2D_FROZEN_FORCED" in os.environ:
+            self.set_option("frozen_forced", float(os.environ["NK2D_FROZEN_FORCED"]))
         # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_TWO_ENDED" in os.environ:
             self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
