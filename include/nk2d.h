@@ -207,7 +207,8 @@ int nk2d_set_frozen_schedule(nk2d_ctx* ctx, const double* sched, int64_t sched_n
    error estimate on every k-th step of a frozen year (one launch each, plus the tendency at the step start): a step whose estimate
    exceeds 1.5 * max(1, recorded estimate) returns -7 as well.  A schedule whose fingerprint is not this context's
    (other options, grid or library build) is refused with -8 before anything runs.
-   nk2d_frozen_fallbacks: how often a frozen year was given up (-7) on this context; nk2d_frozen_resumes: how often one was
+   nk2d_frozen_fallbacks: how often a frozen year was given up (-7) on this context (and how often a one-launch year of option
+   "frozen_phosphorus" was handed back to the launch-per-phase path because a hand-over timed out); nk2d_frozen_resumes: how often one was
    resumed. */
 int nk2d_frozen_fallbacks(nk2d_ctx* ctx, int64_t* n);
 int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
@@ -239,7 +240,18 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    the option): a row of that cache also holds the file-source plane at its Jacobian time, 8 n (3 kv_len + 5 np + np) bytes, and
    the year forms that diagonal plane for each wave's own column, from the state at the step start, at the rows where the
    launch-per-phase path evaluates the Jacobian anew, in a plane the cache owns; any value outside 0 ... 3 is an error; phosphorus
-   contexts are unaffected).  Same device functions, bit-identical results; a year that does not pass the Newton check, or a
+   contexts are unaffected; "frozen_phosphorus" (environment NK2D_FROZEN_PHOSPHORUS), default 0, opt-in, read at every frozen
+   year: the one-launch year for the phosphorus module (module_kind 1, whose Jacobian reads the state through one diagonal plane and
+   whose tracers are coupled inside a ypos column), at three to eight levels per lane, on the lean cache only ("frozen_cache_lean" 1,
+   or 2, which for such a context always means lean; with 0 the year routes as without the option), a row of which is the planes
+   alone, 8 (3 kv_len + 5 np) bytes: the workgroup is one ypos column with its tracers, a wave each, whatever "frozen_by_column" and
+   "frozen_coef_lds" say, and every wave forms that diagonal plane for the column, from the state at the step start, at the rows
+   where the launch-per-phase path evaluates the Jacobian anew, in a plane the cache owns -- 1: the kernel at one wave per SIMD
+   where all its workgroups are resident, otherwise the year routes on as without the option; 2: as 1, and where that flavour is
+   not resident the same kernel within 256 registers (two waves to a SIMD, five to eight levels per lane) if that one is; 3: the
+   256-register flavour wherever it exists; any value outside 0 ... 3 is an error; one and two levels per lane stay out: the
+   by-column workgroup does not exist there and a four-wave team cannot hold three coupled tracers; other modules are unaffected).
+   Same device functions, bit-identical results; a year that does not pass the Newton check, or a
    barrier that times out, is handed to the launch-per-phase path.  Counters by name: "frozen_persistent_years",
    "frozen_team_years" (of them: a four-wave team per column), "frozen_cache_bytes",
    "frozen_launch_us" (device time of those launches), "frozen_cache_pending" (1 while a thread allocates a large cache or pieces),
@@ -248,6 +260,8 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    "frozen_lean_years" (one-launch years run on a lean cache; also counted in "frozen_persistent_years"),
    "frozen_forced_years" (one-launch years only option "frozen_forced" made possible; also counted in "frozen_persistent_years",
    and in "frozen_lean_years" where lean),
+   "frozen_phosphorus_years" (one-launch years of the phosphorus module, option "frozen_phosphorus"; also counted in
+   "frozen_persistent_years" and "frozen_lean_years"), "frozen_two_waves_years" (of them: the years that ran the 256-register flavour),
    "frozen_cache_builds", "frozen_fallbacks", "frozen_resumes"; of the host-side controller: "spec_launches_dropped",
    "spec_front_launches_dropped", "err_estimates_queued", "err_estimates_dropped" (work queued ahead of a verdict); of the
    preconditioner (option "pc_two_ended"): "pc_setup_rounds" (dependent inversion rounds of the last block elimination: ny,

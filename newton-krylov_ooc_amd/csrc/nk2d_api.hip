@@ -234,6 +234,13 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
         c->frozen_forced = (int)value;
         return 0;
     }
+    if (key == "frozen_phosphorus") {
+        // the one-launch year for the phosphorus module, on the lean cache at three to eight levels per lane (nk2d_frozen.hip).  1: one wave
+        // per SIMD where its grid is resident; 2: else the 256-register flavour; 3: that flavour wherever it exists.  Taken at the next frozen year
+        if (value != 0.0 && value != 1.0 && value != 2.0 && value != 3.0) return nk2d_fail(c, "nk2d_set_option: frozen_phosphorus is 0, 1, 2 or 3");
+        c->frozen_phosphorus = (int)value;
+        return 0;
+    }
     if (key == "frozen_cache_piece_mb") {
         if (!(value > 0.0) || !std::isfinite(value)) return nk2d_fail(c, "nk2d_set_option: frozen_cache_piece_mb must be > 0");
         c->frozen_cache_piece_mb = value;
@@ -613,6 +620,9 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_lean_mem_key = 0;
     c->frozen_forced = 0;
     c->frozen_forced_years = 0;
+    c->frozen_phosphorus = 0;
+    c->frozen_two_waves_last = 0;
+    c->frozen_phosphorus_years = c->frozen_two_waves_years = 0;
     c->frozen_cache_piece_allocs = c->frozen_cache_early_requests = 0;
     c->frozen_coef_lds = 15;
     c->frozen_by_column = 1;
@@ -1159,6 +1169,8 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_cache_lean") v = nk2d_frozen_cache_is_lean(c);
     else if (key == "frozen_lean_years") v = c->frozen_lean_years;
     else if (key == "frozen_forced_years") v = c->frozen_forced_years;
+    else if (key == "frozen_phosphorus_years") v = c->frozen_phosphorus_years;
+    else if (key == "frozen_two_waves_years") v = c->frozen_two_waves_years;
     else if (key == "frozen_cache_piece_allocs") v = nk2d_frozen_cache_piece_allocs(c);
     else if (key == "frozen_cache_early_requests") v = c->frozen_cache_early_requests;
     else if (key == "frozen_fallbacks") v = c->frozen_fallbacks;

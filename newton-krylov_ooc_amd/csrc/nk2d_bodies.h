@@ -443,6 +443,23 @@ __device__ __forceinline__ void forced_upr_col(const DevP& P, const double* __re
     store_col<E>(UPR, j, lane, upr);
 }
 
+// phosphorus module: column j of UPR = d uptake / d po4 = mu light hs / (po4 + hs)^2 at the linearisation state `ylin`, whose
+// tracer 0 is po4 (phosphorus.py:97-103).  The one place these expressions live: the Jacobian launch (jac_core) and the one-launch
+// frozen year of the module (k_frozen_persistent, option "frozen_phosphorus") both call it.  MPY: how the state is loaded
+template <int E, int MPY = 0>
+__device__ __forceinline__ void phos_upr_col(const DevP& P, const double* __restrict__ ylin, double* __restrict__ UPR, int j, int lane) {
+    double po4[E], light[E], upr[E];
+    load_col<E, MPY>(ylin, j, lane, po4);
+    load_col<E>(P.LIGHT, j, lane, light);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const double den = po4[e] + P.ph_hs;
+        const double lim_d = P.ph_hs / (den * den);
+        upr[e] = ((lane * E + e) < P.nz) ? (P.ph_mu * light[e]) * lim_d : 0.0;
+    }
+    store_col<E>(UPR, j, lane, upr);
+}
+
 // the same from a vertical mixing column held in registers (kvp: its bundle in memory, read only for the source plane of
 // a forced module with a thresholded sink)
 template <int E, int MP = 0>
@@ -464,16 +481,7 @@ __device__ __forceinline__ void jac_core(const DevP& P, const double (&kv)[E], c
         forced_upr_col<E>(P, ylin, kvp + P.np, UPR, j, lane);
     } else if (ylin != nullptr) {
         // d uptake / d po4 at the linearisation state (phosphorus.py:97-103)
-        double po4[E], light[E], upr[E];
-        load_col<E>(ylin, j, lane, po4);
-        load_col<E>(P.LIGHT, j, lane, light);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const double den = po4[e] + P.ph_hs;
-            const double lim_d = P.ph_hs / (den * den);
-            upr[e] = ((lane * E + e) < P.nz) ? (P.ph_mu * light[e]) * lim_d : 0.0;
-        }
-        store_col<E>(UPR, j, lane, upr);
+        phos_upr_col<E>(P, ylin, UPR, j, lane);
     }
 }
 
@@ -2211,7 +2219,7 @@ struct FrozenRow {
     int n_iter, m;               // simplified-Newton iterations, sweeps per solve
     double h;                    // step size
     int err;                     // 1: SciPy's error estimate of this step is evaluated too (its partials to row 3 i + 2 of STEP_PART)
-    int upr;                     // 1: the row takes a new Jacobian (t_jac differs from the row before): a thresholded forced module forms UPR anew
+    int upr;                     // 1: the row takes a new Jacobian (t_jac differs from the row before): a thresholded forced module and phosphorus form UPR anew
     double cre, ccr, cci;        // shifts of the row's line factorisation (h_lu): what the LEAN year factorises with in the row's first phase
 };
 
@@ -2232,6 +2240,7 @@ struct FrozenArgs {
     int by_column;               // 1: a workgroup is ONE ypos column with all its tracers (a wave each) instead of adjacent columns of one tracer
     // option "frozen_forced" bit 2 (forced module with a thresholded sink, lean cache): the rows' file-source planes at their Jacobian
     // times, [n][np] behind J in the slab (a cache in pieces: PieceTab::oS), and 1 where the year forms UPR from them
+    // (option "frozen_phosphorus": upr_on alone -- the year forms UPR from the state and the context's static light plane)
     const double* SRC;
     int upr_on;
 };
@@ -2259,6 +2268,12 @@ __device__ __forceinline__ void tend_at_body(const DevP& P, const double* __rest
     load_col<E, MP>(kvp, j, lane, kv);
     tend_col<E, KIND>(P, cf, c, cs, cn, kv, tr, lane, ff);
     if constexpr (KIND == 2) forced_sources<E>(P, kvp, j, lane, c, ff);
+    if constexpr (KIND == 1) {
+        // (phosphorus: the other two tracers of the column, as commit_tend_body forms them for the launch path's step boundary)
+        double u1[E], u2[E];
+        phos_load_others<E>(P, tr, j, lane, y, u1, u2);
+        phos_sources<E>(P, tr, j, lane, c, u1, u2, cf.dzr, ff);
+    }
     store_col<E, MP>(f, task, lane, ff);
 }
 

@@ -127,7 +127,10 @@ struct nk2d_ctx {
     double* STEP_PART;      // frozen year: norm partials of the last two Newton iterations of every step, rows of ncol
     size_t step_part_rows;  // rows allocated
     double* STEP_NORM;  // [3 * NK2D_OWN_REC_CAP] per step of a frozen year: sum((dW/scale)^2) of its last and last-but-one iteration, sum((err/scale)^2)
-    int64_t frozen_fallbacks;   // frozen years rejected by the a-posteriori Newton check (nk2d_frozen_fallbacks)
+    // frozen years given up with -7: rejected by the a-posteriori Newton check or by a sampled error estimate (nk2d_frozen_fallbacks).
+    // For module_kind 1 ALSO the one-launch years of option "frozen_phosphorus" that a hand-over time-out handed back to the
+    // launch-per-phase path, which then reran them (run_replay; for the other modules such a hand-back shows in nbarrier_timeouts only)
+    int64_t frozen_fallbacks;
     // the frozen year of a small grid in one launch on a schedule cache (k_frozen_persistent, nk2d_kernels.hip)
     void* frozen_cache;
     int frozen_persistent;          // option "frozen_persistent": 1 = where eligible (default), 0 = never
@@ -151,6 +154,11 @@ struct nk2d_ctx {
     // option "frozen_forced": the one-launch year for the file-driven forced module (kind 2) where it has none by default
     int frozen_forced;                // bit mask, default 0.  1: linear sources at five to eight levels per lane; 2: a thresholded sink (lean cache only)
     int64_t frozen_forced_years;      // one-launch years only that option made possible (also counted in frozen_persistent_years)
+    // option "frozen_phosphorus": the one-launch year for the phosphorus module (kind 1), on the lean cache, three to eight levels per lane
+    int frozen_phosphorus;            // default 0.  1: one wave per SIMD; 2: the 256-register flavour where that one is not resident; 3: it wherever it exists
+    int frozen_two_waves_last;        // 1: the one-launch year just run was the 256-register flavour (k_frozen_persistent_w2)
+    int64_t frozen_phosphorus_years;  // one-launch years of that module (also counted in frozen_persistent_years and frozen_lean_years)
+    int64_t frozen_two_waves_years;   // of them: the years that ran the 256-register flavour
     int frozen_cache_early;           // option "frozen_cache_early": with pieces, the year that records a schedule asks for its pieces when it ends
     int64_t frozen_cache_piece_allocs, frozen_cache_early_requests;   // counters: pieces allocated so far, early requests made
     uint64_t frozen_seen_key; int frozen_seen_years;   // the schedule last seen by nk2d_frozen_persistent and its years so far

@@ -112,330 +112,21 @@ __device__ __forceinline__ void frozen_factor_phase(const DevP& P, const FusedAr
 // launch-per-phase path runs at every "LU" event) with the row's shifts: it leaves pivots and PCR tables of the wave's own
 // column there, and the row's later phases -- the error estimate included -- read them as they read a full cache's.  A
 // column's tables are written and read by its own workgroup only: nothing of them crosses the hand-over.
+// The body of the kernel is the text of nk2d_frozen_body.inc, which its two entries include: k_frozen_persistent, and -- phosphorus
+// from five levels per lane -- k_frozen_persistent_w2, the same within 256 registers (as k_stream has k_stream_w2).  Included text
+// rather than a device function called by both: through a function the instantiations of k_frozen_persistent came out with
+// other register counts (1 to 14 vector registers up or down on 38 of 80); as text they are what they were.
 template <int E, int KIND, int TEAM = 0, int PIECES = 0, int LEAN = 0>
 __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typename FrozenArgOf<PIECES>::type A) {
-    constexpr int XCD = 0, NB = 1;      // (rounds 2 - 3 also had all workgroups on one XCD and a grid barrier between the phases)
-    __shared__ int lds_ok;
-    __shared__ double team_lds[TEAM ? sizeof(TeamLds<E, 3>) / sizeof(double) : 1];
-    constexpr int MPX = XCD ? 2 : 1;
-    const int lane = threadIdx.x & 63;
-    int wg = (int)blockIdx.x;
-    const int tw = uni_i((int)(threadIdx.x >> 6));                      // TEAM: the wave's place in its team
-    // the column of this wave.  A team: the workgroup's.  A wave per column: adjacent columns of one tracer to a workgroup, or
-    // -- `by_column` -- the workgroup is ONE ypos column and its waves that column's tracers (what is the same for every tracer
-    // of a ypos column is then shared through LDS)
-    const bool by_col = !TEAM && !XCD && NB != 0 && A.by_column != 0;
-    const int wave = TEAM ? uni_i(wg) : (by_col ? uni_i(tw * P.ny + wg) : uni_i(wg * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6)));
-    const bool col_wave = wave < P.ncol && (!by_col || (tw < P.tc && wg < P.ny));
-    // NB: neighbour-to-neighbour hand-over instead of the grid barrier.  The unit is the workgroup: one column (teams), or
-    // the columns of its waves -- then the workgroup to the left matters if its first column has a left neighbour, the one to
-    // the right if its last column has a right neighbour (a tracer boundary inside the workgroup needs nothing)
-    int nb_left, nb_right;
-    if constexpr (TEAM) {
-        const int nb_j = wave % P.ny;
-        nb_left = (nb_j > 0) ? wg - 1 : -1;
-        nb_right = (nb_j < P.ny - 1) ? wg + 1 : -1;
-    } else if (by_col) {
-        nb_left = (wg > 0) ? wg - 1 : -1;
-        nb_right = (wg < P.ny - 1) ? wg + 1 : -1;
-    } else {
-        const int wpb = (int)(blockDim.x >> 6);
-        const int c0 = wg * wpb, cl = min(c0 + wpb - 1, P.ncol - 1);
-        nb_left = (c0 % P.ny > 0) ? wg - 1 : -1;
-        nb_right = (cl % P.ny < P.ny - 1) ? wg + 1 : -1;
-    }
-    NeighbourSync nbs{(unsigned*)((char*)A.arrive + 8192), A.abort_flag, wg, nb_left, nb_right, 0u, &lds_ok, A.spin_ticks, A.fences};
-    const size_t nv = A.C.nv;
-    int swapY = 0, swapZ = 0, status = 0, done = 0;
-    int pc_p = 0, pc_r = 0;     // PIECES: row i is row pc_r of piece pc_p (i = pc_p rows + pc_r, kept by counting: no division)
-    (void)pc_p; (void)pc_r;
-#define FZ_Y (swapY ? A.YOLD : A.Y)
-#define FZ_YOLD (swapY ? A.Y : A.YOLD)
-#define FZ_Z (swapZ ? A.ZN : A.Z)
-#define FZ_ZN (swapZ ? A.Z : A.ZN)
-#define FZ_SYNC() \
-    if (!nbs.sync()) { status = 1; goto finish; }
-    // a wave per column, three and more levels per lane (option "frozen_coef_lds"): the static coefficients of the wave's column
-    // in LDS for the whole year (dynamic shared memory of the launch: NK2D_COEF_LDS_DOUBLES(E) doubles per wave)
-    constexpr bool COEF_LDS = NB != 0 && !TEAM && !XCD && E >= 3;
-    // Layout of the dynamic shared memory.  Adjacent columns: per wave [coefficients][W].  By column: [coefficients of the ypos
-    // column][step block: 3 mixing columns, JL, JU][per wave: W][per wave: pivots of the real system] (each part present where
-    // its bit of A.coef_lds is set; frozen_lds_doubles() on the host computes the same)
-    extern __shared__ double dyn_lds[];
-    const bool w_in_lds = COEF_LDS && (A.coef_lds & 2) != 0;
-    const bool step_in_lds = COEF_LDS && by_col && (A.coef_lds & 4) != 0;
-    const bool piv_in_lds = COEF_LDS && by_col && (A.coef_lds & 8) != 0;
-    const int nwv = (int)(blockDim.x >> 6);
-    double* my_coef;
-    double* my_w;
-    double* step_lds = nullptr;
-    double* my_piv = nullptr;
-    if (by_col) {
-        double* p = dyn_lds;
-        my_coef = p; p += NK2D_COEF_LDS_DOUBLES(E);
-        step_lds = p; p += step_in_lds ? 5 * E * 64 : 0;
-        my_w = p + (size_t)tw * (3 * E * 64); p += w_in_lds ? (size_t)nwv * 3 * E * 64 : 0;
-        my_piv = p + (size_t)tw * (E * 64);
-    } else {
-        my_coef = dyn_lds + (size_t)(threadIdx.x >> 6) * (NK2D_COEF_LDS_DOUBLES(E) + (w_in_lds ? 3 * E * 64 : 0));
-        my_w = my_coef + NK2D_COEF_LDS_DOUBLES(E);
-    }
-    const LdsSrc L = {my_coef, my_w, step_lds, my_piv};
-    (void)L;
-    if constexpr (COEF_LDS) {
-        if (A.coef_lds && col_wave && (!by_col || tw == 0)) {
-            ColCoef<E> cf;
-            load_coef<E>(P, wave % P.ny, lane, cf);
-            store_coef_lds<E>(my_coef, lane, cf);
-        }
-        if (by_col && A.coef_lds) __syncthreads();      // (the other tracers' waves read what wave 0 stored)
-    }
-    int lds_step = -1;      // the step whose constants the step block / the pivots hold
-    (void)lds_step;
-    // first attempt of the year: Z0 = 0, W0 = 0 (radau.py:445-446)
-    if (col_wave && (!TEAM || tw == 0)) {
-        double zero[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) zero[e] = 0.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            store_col<E, MPX>(FZ_Z + i * nv, wave, lane, zero);
-            store_col<E, (TEAM ? MPX : 0)>(A.W + i * nv, wave, lane, zero);
-            if constexpr (COEF_LDS) {
-                if (w_in_lds) w_lds_put<E>(my_w, i, lane, zero);
-            }
-        }
-    }
-    FZ_SYNC()
-    for (int i = 0; i < A.n; ++i) {
-        const FrozenRow R = A.rows[i];
-        const int n_iter = uni_i(R.n_iter), m = uni_i(R.m);
-        const bool last_row = i == A.n - 1;
-        // PIECES: the row's tables -- the piece's base (the same for every lane of every wave: one load, the value in scalar
-        // registers) + fixed offsets + r stride; the slab flavour forms base + i stride where it uses them, as it always did
-        RowTabs T = {};
-        const double* kv_prev = nullptr;    // the mixing plane at the step start = the last stage plane of row i - 1
-        (void)T; (void)kv_prev;
-        if constexpr (PIECES) {
-            double* const base = uni_p(A.T.base[pc_p]);
-            T = piece_row_tabs(A.C, A.T, base, pc_r);
-            if (i > 0 && uni_i(R.err) != 0) {
-                // (row i - 1 may be the last row of the piece before: resolved on its own, on the few rows that carry an estimate)
-                const double* pb = pc_r > 0 ? base : uni_p(A.T.base[pc_p - 1]);
-                const int pr = pc_r > 0 ? pc_r - 1 : A.T.rows - 1;
-                kv_prev = pb + ((size_t)pr * 3 + 2) * A.C.kv_len;
-            }
-            if (++pc_r == A.T.rows) { pc_r = 0; ++pc_p; }
-        }
-        const double* kvb = PIECES ? T.KV : A.C.KV + (size_t)i * 3 * A.C.kv_len;
-        const double* J = PIECES ? T.J : A.C.J + (size_t)i * 5 * A.C.np;
-        if constexpr (KIND == 2 && LEAN) {
-            // a thresholded sink (option "frozen_forced" bit 2): UPR = -d sms / d c of the wave's own column, at the rows where the
-            // launch path evaluates the Jacobian anew, from the state at the step start (its own y_new of the row before, or the
-            // year's input) and the file source at the row's Jacobian time -- jac_core's expressions, into the plane P.UPR names
-            // (the cache's own).  The row's phases read it through line_diag_from: the wave's own stores, read back by itself
-            // (every wave of a team forms the column for itself: the same values to the same places)
-            if (A.upr_on != 0 && uni_i(R.upr) != 0 && col_wave) {
-                const double* sp = PIECES ? T.SRC : A.SRC + (size_t)i * A.C.np;
-                forced_upr_col<E, MPX>(P, FZ_Y, sp, const_cast<double*>(P.UPR), wave % P.ny, lane);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        }
-        // SciPy's error estimate on this step too (every "frozen_err_check"-th: the host compares it with what the recorded
-        // step was accepted with).  Three phases of their own, one wave per column: the tendency at the step start before the
-        // Newton iterations, the estimate behind the last of them -- which is then an ordinary iteration --, the end of the step
-        const bool with_err = uni_i(R.err) != 0 && !last_row && i > 0;
-        if (with_err) {
-            if (col_wave && (!TEAM || tw == 0))
-                tend_at_body<E, KIND, MPX>(P, FZ_Y, PIECES ? kv_prev : A.C.KV + ((size_t)(i - 1) * 3 + 2) * A.C.kv_len, A.F, wave, lane);
-            FZ_SYNC()
-        }
-        for (int k = 0; k < n_iter; ++k) {
-            int src = 0;
-            for (int it = 0; it < m; ++it) {
-                const bool do_stage = it == 0, first = it == 0, do_update = it == m - 1, delta = m == 2;
-                const bool is_final = do_update && k == n_iter - 1 && !last_row && !with_err;
-                FusedArgs FA = {};
-                FA.st.y = FZ_Y; FA.st.z = FZ_Z; FA.st.w = A.W;
-                FA.st.zout = (do_stage && do_update) ? FZ_ZN : FZ_Z;
-                FA.st.kv[0] = kvb; FA.st.kv[1] = kvb + A.C.kv_len; FA.st.kv[2] = kvb + 2 * A.C.kv_len;
-                FA.st.br = A.BR; FA.st.bcr = A.BCR; FA.st.bci = A.BCI;
-                FA.st.nv = nv; FA.st.mreal = R.mreal; FA.st.mcr = R.mcr; FA.st.mci = R.mci;
-                FA.sw.JL = J; FA.sw.JU = J + A.C.np; FA.sw.JS = J + 2 * A.C.np; FA.sw.JN = J + 3 * A.C.np; FA.sw.JC = J + 4 * A.C.np;
-                // LEAN: this phase factorises (the first of the row); the one row of tables
-                const bool fac = LEAN != 0 && k == 0 && it == 0;
-                // (The factorising bodies read the grid's parameters where the launch put them, in the kernel-argument segment, whose
-                // first argument P is: with them reading the kernel's own copy of P, the compiler -- ROCm 7.2's clang 22, instcombine's
-                // rewrite of an argument copy that is only read -- crashes on the forced module at one level per lane.  Same values.)
-                const DevP& PK = *(const DevP*)__builtin_amdgcn_kernarg_segment_ptr();
-                (void)PK;
-                if constexpr (LEAN) {
-                    FA.sw.fr_inv = A.C.fr_inv; FA.sw.fc_invr = A.C.fc_invr; FA.sw.fc_invi = A.C.fc_invi;
-                    FA.sw.fr_tab = A.C.fr_tab; FA.sw.fc_tabr = A.C.fc_tabr; FA.sw.fc_tabi = A.C.fc_tabi;
-                    FA.sw.cre = R.cre; FA.sw.ccr = R.ccr; FA.sw.cci = R.cci;
-                } else if constexpr (PIECES) {
-                    FA.sw.fr_inv = T.fr_inv; FA.sw.fc_invr = T.fc_invr; FA.sw.fc_invi = T.fc_invi;
-                    FA.sw.fr_tab = T.fr_tab; FA.sw.fc_tabr = T.fc_tabr; FA.sw.fc_tabi = T.fc_tabi;
-                } else {
-                    FA.sw.fr_inv = A.C.fr_inv + (size_t)i * nv; FA.sw.fc_invr = A.C.fc_invr + (size_t)i * nv;
-                    FA.sw.fc_invi = A.C.fc_invi + (size_t)i * nv;
-                    FA.sw.fr_tab = A.C.fr_tab + (size_t)i * A.C.ntab; FA.sw.fc_tabr = A.C.fc_tabr + (size_t)i * A.C.ntab;
-                    FA.sw.fc_tabi = A.C.fc_tabi + (size_t)i * A.C.ntab;
-                }
-                FA.sw.f32 = 0;
-                FA.sw.br = A.BR; FA.sw.bcr = A.BCR; FA.sw.bci = A.BCI;
-                FA.sw.xr_old = src ? A.XR[1] : A.XR[0]; FA.sw.xcr_old = src ? A.XCR[1] : A.XCR[0];
-                FA.sw.xci_old = src ? A.XCI[1] : A.XCI[0];
-                FA.sw.xr_new = src ? A.XR[0] : A.XR[1]; FA.sw.xcr_new = src ? A.XCR[0] : A.XCR[1];
-                FA.sw.xci_new = src ? A.XCI[0] : A.XCI[1];
-                FA.sw.first = first ? 1 : 0;
-                FA.part = (k == n_iter - 1) ? A.STEP_PART + (size_t)(3 * i) * P.ncol
-                                            : ((k == n_iter - 2) ? A.STEP_PART + (size_t)(3 * i + 1) * P.ncol : A.PART);
-                FA.do_stage = do_stage ? 1 : 0; FA.do_update = do_update ? 1 : 0; FA.delta = delta ? 1 : 0;
-                if constexpr (COEF_LDS) {
-                    if (step_in_lds && lds_step != i) {
-                        // first phase of a step: what is constant over the step's iterations goes to LDS once -- the three mixing
-                        // columns and JL, JU of the ypos column shared out over the workgroup's waves, each wave's own pivots
-                        for (int r = tw; r < 5; r += nwv) {
-                            double v[E];
-                            // (selects, not an index: a struct indexed at run time would live in scratch memory)
-                            const double* src = (r == 0) ? FA.st.kv[0] : ((r == 1) ? FA.st.kv[1] : ((r == 2) ? FA.st.kv[2]
-                                                : ((r == 3) ? FA.sw.JL : FA.sw.JU)));
-                            load_col<E, MPX>(src, wave % P.ny, lane, v);
-                            w_lds_put<E>(step_lds, r, lane, v);
-                        }
-                        if constexpr (!LEAN) {
-                        if (piv_in_lds && col_wave) {
-                            double v[E];
-                            load_col<E>(FA.sw.fr_inv, wave, lane, v);
-                            w_lds_put<E>(my_piv, 0, lane, v);
-                        }
-                        }       // (LEAN: the pivots do not exist yet -- filled behind the factorising phase below)
-                        lds_step = i;
-                        __syncthreads();
-                    }
-                }
-                if (is_final) {
-                    FinalArgs Fin;
-                    Fin.ynew = FZ_YOLD;
-                    Fin.znext = do_stage ? FZ_ZN : FZ_Z;
-                    Fin.x0 = R.x0; Fin.x1 = R.x1; Fin.x2 = R.x2;
-                    Fin.nblk_cols = 0;
-                    if constexpr (TEAM) {
-                        if constexpr (LEAN) {
-                            if (col_wave && fac)
-                                newton_team_body<E, KIND, 1, 1, 4, 1, MPX>(PK, FA, *reinterpret_cast<TeamLds<E, 3>*>(team_lds), wave, tw, lane, &Fin);
-                        }
-                        if (col_wave && !fac)
-                            newton_team_body<E, KIND, 0, 1, 4, 1, MPX>(P, FA, *reinterpret_cast<TeamLds<E, 3>*>(team_lds), wave, tw, lane, &Fin);
-                    } else if (col_wave && fac) {
-                        if constexpr (LEAN && COEF_LDS) frozen_factor_phase<E, KIND, MPX, 1>(PK, FA, wave, lane, &Fin, &L, A.coef_lds, w_in_lds, piv_in_lds ? my_piv : nullptr);
-                        else if constexpr (LEAN) newton_fused_body<E, KIND, 1, 1, MPX, 1>(PK, FA, wave, lane, &Fin);
-                    } else if (col_wave) {
-                        bool taken = false;
-                        if constexpr (KIND == 0 && E <= 2) {
-                            if (m == 1) { newton_single_body<E, MPX, 1>(P, FA, wave, lane, &Fin); taken = true; }
-                        }
-                        if constexpr (COEF_LDS) {
-                            if (step_in_lds && piv_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 15>(P, FA, wave, lane, &Fin, &L); taken = true; }
-                            else if (step_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 7>(P, FA, wave, lane, &Fin, &L); taken = true; }
-                            else if (w_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 3>(P, FA, wave, lane, &Fin, &L); taken = true; }
-                            else if (A.coef_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 1>(P, FA, wave, lane, &Fin, &L); taken = true; }
-                        }
-                        if (!taken) newton_fused_body<E, KIND, 0, 1, MPX, 1>(P, FA, wave, lane, &Fin);
-                    }
-                    swapY ^= 1;
-                    if (do_stage) swapZ ^= 1;
-                } else {
-                    if constexpr (TEAM) {
-                        if constexpr (LEAN) {
-                            if (col_wave && fac)
-                                newton_team_body<E, KIND, 1, 1, 4, 0, MPX>(PK, FA, *reinterpret_cast<TeamLds<E, 3>*>(team_lds), wave, tw, lane, nullptr);
-                        }
-                        if (col_wave && !fac)
-                            newton_team_body<E, KIND, 0, 1, 4, 0, MPX>(P, FA, *reinterpret_cast<TeamLds<E, 3>*>(team_lds), wave, tw, lane, nullptr);
-                    } else if (col_wave && fac) {
-                        if constexpr (LEAN && COEF_LDS) frozen_factor_phase<E, KIND, MPX, 0>(PK, FA, wave, lane, nullptr, &L, A.coef_lds, w_in_lds, piv_in_lds ? my_piv : nullptr);
-                        else if constexpr (LEAN) newton_fused_body<E, KIND, 1, 1, MPX, 0>(PK, FA, wave, lane);
-                    } else if (col_wave) {
-                        bool taken = false;
-                        if constexpr (KIND == 0 && E <= 2) {
-                            if (m == 1) { newton_single_body<E, MPX, 0>(P, FA, wave, lane); taken = true; }
-                        }
-                        if constexpr (COEF_LDS) {
-                            if (step_in_lds && piv_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 15>(P, FA, wave, lane, nullptr, &L); taken = true; }
-                            else if (step_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 7>(P, FA, wave, lane, nullptr, &L); taken = true; }
-                            else if (w_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 3>(P, FA, wave, lane, nullptr, &L); taken = true; }
-                            else if (A.coef_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 1>(P, FA, wave, lane, nullptr, &L); taken = true; }
-                        }
-                        if (!taken) newton_fused_body<E, KIND, 0, 1, MPX, 0>(P, FA, wave, lane);
-                    }
-                    if (do_stage && do_update) swapZ ^= 1;
-                }
-                src = 1 - src;
-                FZ_SYNC()
-            }
-        }
-        if (with_err) {
-            if (col_wave && (!TEAM || tw == 0)) {
-                ErrArgs EA = {};
-                EA.sw.JL = J; EA.sw.JU = J + A.C.np; EA.sw.JS = J + 2 * A.C.np; EA.sw.JN = J + 3 * A.C.np; EA.sw.JC = J + 4 * A.C.np;
-                EA.sw.fr_inv = LEAN ? A.C.fr_inv : (PIECES ? T.fr_inv : A.C.fr_inv + (size_t)i * nv);
-                EA.sw.fr_tab = LEAN ? A.C.fr_tab : (PIECES ? T.fr_tab : A.C.fr_tab + (size_t)i * A.C.ntab);
-                EA.sw.xr_old = A.XR[0]; EA.sw.xr_new = A.XR[1];
-                EA.f = A.F; EA.z = FZ_Z; EA.y = FZ_Y; EA.nv = nv; EA.h = R.h;
-                EA.part = A.STEP_PART + (size_t)(3 * i + 2) * P.ncol;
-                EA.stage = 0; EA.last = 1;
-                err_fused_body<E, KIND, MPX>(P, EA, wave, lane);
-            }
-            FZ_SYNC()
-            if (col_wave && (!TEAM || tw == 0)) {
-                FinalArgs Fin;
-                Fin.ynew = FZ_YOLD;
-                Fin.znext = FZ_ZN;
-                Fin.x0 = R.x0; Fin.x1 = R.x1; Fin.x2 = R.x2;
-                Fin.nblk_cols = 0;
-                step_tail_body<E, MPX>(FZ_Y, FZ_Z, nv, Fin, A.W, wave, lane);
-                if constexpr (COEF_LDS) {
-                    if (w_in_lds) {     // (this rare phase writes W to memory: into the column's LDS copy from there)
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-                        for (int r = 0; r < 3; ++r) {
-                            double wv[E];
-                            load_col<E, (TEAM ? MPX : 0)>(A.W + r * nv, wave, lane, wv);
-                            w_lds_put<E>(my_w, r, lane, wv);
-                        }
-                    }
-                }
-            }
-            swapY ^= 1;
-            swapZ ^= 1;
-            FZ_SYNC()
-        }
-        done = i + 1;
-    }
-finish:
-    if constexpr (COEF_LDS) {
-        if (w_in_lds && col_wave) {      // W of the last phase back where the launch-per-phase path keeps it
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                double wv[E];
-                w_lds_get<E>(my_w, r, lane, wv);
-                store_col<E>(A.W + r * nv, wave, lane, wv);
-            }
-        }
-    }
-    // no barrier behind the last phase: every workgroup reports a failure of its own (the host cleared `out`), the first the
-    // rest -- a workgroup that gave up raised the abort flag, its neighbours give up on it in turn
-    if (status != 0 && threadIdx.x == 0) A.out[0] = (double)status;
-    if (wg == 0 && threadIdx.x == 0) {
-        A.out[1] = (double)done; A.out[2] = (double)swapY; A.out[3] = (double)swapZ; A.out[4] = (double)nbs.phase;
-    }
-#undef FZ_SYNC
-#undef FZ_Y
-#undef FZ_YOLD
-#undef FZ_Z
-#undef FZ_ZN
+#include "nk2d_frozen_body.inc"
+}
+// The same within 256 registers, so that a SIMD holds TWO waves (option "frozen_phosphorus" 2 and 3; phosphorus on the lean cache from
+// five levels per lane, where a by-column workgroup of three waves at a wave per SIMD leaves the chip room for one workgroup per
+// compute unit: 416 ypos columns are then two workgroups on each).  What does not fit the registers lives in scratch memory.
+template <int E, int PIECES>
+__global__ void __launch_bounds__(NK2D_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) k_frozen_persistent_w2(DevP P, typename FrozenArgOf<PIECES>::type A) {
+    constexpr int KIND = 1, TEAM = 0, LEAN = 1;
+#include "nk2d_frozen_body.inc"
 }
 
 // the cache of everything a schedule fixes besides the state; rebuilt when another schedule comes
@@ -484,6 +175,14 @@ struct nk2d_frozen_cache {
 
 // a forced module whose file source has a sink threshold: its Jacobian reads the state (the diagonal plane UPR)
 static bool frozen_thres(const nk2d_ctx* c) { return c->kind == 2 && c->d.sms_nrec > 0 && c->d.sink_thres > 0.0; }
+
+// phosphorus (module_kind 1) where option "frozen_phosphorus" lets it take the one-launch year: on the lean cache ("frozen_cache_lean" 1, or
+// 2, which for such a context always means lean), at three to eight levels per lane -- the workgroup is then one ypos column with
+// its tracers, a wave each.  One and two levels per lane stay out: the by-column workgroup does not exist there, and the
+// four-wave teams cannot hold three coupled tracers
+static bool frozen_phos(const nk2d_ctx* c) {
+    return c->kind == 1 && c->frozen_phosphorus != 0 && c->frozen_cache_lean != 0 && c->E >= 3 && c->E <= 8 && c->tc <= NK2D_WAVES_PER_BLOCK;
+}
 
 // doubles of a row of the cache (lean: the planes only; src: and the file-source plane at the Jacobian time)
 static size_t frozen_row_doubles(const nk2d_ctx* c, bool lean, bool src) {
@@ -536,6 +235,7 @@ static uint64_t sched_key(const double* sched, int64_t n) {
 // file-source planes of option "frozen_forced" bit 2)
 static const uint64_t FROZEN_LEAN_KEY = 0xC2B2AE3D27D4EB4Full;
 static const uint64_t FROZEN_SRC_KEY = 0x165667B19E3779F9ull;
+static const uint64_t FROZEN_PHOS_KEY = 0x27D4EB2F165667C5ull;      // (... and the lean cache of a phosphorus context, option "frozen_phosphorus")
 uint64_t nk2d_frozen_key(const nk2d_ctx* c, const double* sched, int64_t n) {
     return sched_key(sched, n) ^ (uint64_t)nk2d_fingerprint(c) ^ ((uint64_t)(c->frozen_err_check + 1) * 0x9E3779B97F4A7C15ull);
 }
@@ -634,7 +334,7 @@ static size_t frozen_lds_doubles(int E, int bits, bool by_column, int nwaves) {
 }
 
 template <class K, class ARGS>
-static hipError_t launch_resident(nk2d_ctx* c, K kernel, dim3 grid, dim3 block, DevP& P, ARGS& A, size_t lds_bytes = 0) {
+static hipError_t launch_resident(nk2d_ctx* c, K kernel, dim3 grid, dim3 block, DevP& P, ARGS& A, size_t lds_bytes = 0, bool check_only = false) {
     int per_cu = 0;
     hipError_t rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)block.x, lds_bytes);
     if (rc != hipSuccess) return rc;
@@ -642,6 +342,7 @@ static hipError_t launch_resident(nk2d_ctx* c, K kernel, dim3 grid, dim3 block, 
     rc = hipGetDeviceProperties(&prop, c->dev);
     if (rc != hipSuccess) return rc;
     if ((long long)per_cu * prop.multiProcessorCount < (long long)grid.x) return hipErrorCooperativeLaunchTooLarge;
+    if (check_only) return hipSuccess;      // (the caller only asks whether the chip holds the grid)
     if (std::getenv("NK2D_DIAG_COOPERATIVE")) {
         // diagnostic only (profiles/r04_slowdown_ab.log): the launch as rounds 2 - 3 made it, through the runtime's cooperative queue
         void* args[2] = {&P, &A};
@@ -687,6 +388,33 @@ static hipError_t launch_frozen(nk2d_ctx* c, bool team, dim3 grid, DevP& P, type
     const bool forced = c->kind == 2;
     if (team) return forced ? launch_frozen_e<2, 1, PIECES, LEAN>(c, grid, P, A) : launch_frozen_e<0, 1, PIECES, LEAN>(c, grid, P, A);
     return forced ? launch_frozen_e<2, 0, PIECES, LEAN>(c, grid, P, A) : launch_frozen_e<0, 0, PIECES, LEAN>(c, grid, P, A);
+}
+
+// phosphorus (option "frozen_phosphorus"): always by column and lean; `two_waves`: the 256-register entry (five to eight levels per lane)
+template <int E, int PIECES>
+static hipError_t launch_frozen_phos_one(nk2d_ctx* c, DevP& P, typename FrozenArgOf<PIECES>::type& A, bool two_waves, bool check_only) {
+    const dim3 grid((unsigned)c->ny), block((unsigned)(64 * c->tc));
+    const size_t lds = sizeof(double) * frozen_lds_doubles(E, A.coef_lds, true, c->tc);
+    if constexpr (E >= 5) {
+        if (two_waves) return launch_resident(c, k_frozen_persistent_w2<E, PIECES>, grid, block, P, A, lds, check_only);
+    } else if (two_waves) {
+        return hipErrorInvalidValue;
+    }
+    return launch_resident(c, k_frozen_persistent<E, 1, 0, PIECES, 1>, grid, block, P, A, lds, check_only);
+}
+template <int PIECES>
+static hipError_t launch_frozen_phos(nk2d_ctx* c, DevP& P, typename FrozenArgOf<PIECES>::type& A, bool two_waves, bool check_only = false) {
+    if (!A.by_column || c->tc > NK2D_WAVES_PER_BLOCK) return hipErrorInvalidValue;
+    switch (c->E) {
+        case 3: return launch_frozen_phos_one<3, PIECES>(c, P, A, two_waves, check_only);
+        case 4: return launch_frozen_phos_one<4, PIECES>(c, P, A, two_waves, check_only);
+        case 5: return launch_frozen_phos_one<5, PIECES>(c, P, A, two_waves, check_only);
+        case 6: return launch_frozen_phos_one<6, PIECES>(c, P, A, two_waves, check_only);
+        case 7: return launch_frozen_phos_one<7, PIECES>(c, P, A, two_waves, check_only);
+        case 8: return launch_frozen_phos_one<8, PIECES>(c, P, A, two_waves, check_only);
+        default: break;
+    }
+    return hipErrorInvalidValue;
 }
 
 // the slab of a schedule cache with room for `cap` rows from a thread of the library's own (hipMalloc of 120 GB: 0.03 - 3 s);
@@ -771,10 +499,11 @@ static int frozen_adopt(nk2d_ctx* c, nk2d_frozen_cache* fc) {
 
 // is the one-launch year made for this context and schedule?
 static bool frozen_eligible(const nk2d_ctx* c, const double* sched, int64_t n) {
-    // a Jacobian that reads the state: never for phosphorus; a forced module with a thresholded sink with option "frozen_forced" bit 2,
-    // on the lean cache only (its full cache -- factorisations ahead of the state -- cannot exist)
+    // a Jacobian that reads the state: a forced module with a thresholded sink with option "frozen_forced" bit 2, phosphorus with
+    // option "frozen_phosphorus" -- both on the lean cache only (their full cache -- factorisations ahead of the state -- cannot exist)
     const bool thres = frozen_thres(c);
-    const bool needs_state = c->kind == 1 || (thres && !((c->frozen_forced & 2) && c->frozen_cache_lean != 0));
+    const bool phos = frozen_phos(c);
+    const bool needs_state = (c->kind == 1 && !phos) || (thres && !((c->frozen_forced & 2) && c->frozen_cache_lean != 0));
     if (!c->frozen_persistent || needs_state || c->hist_n != 0 || c->norm_hook || n < 1) return false;
     // the cache holds the factorisation in double precision only: with option "factor_fp32" the recorded year read the single
     // precision copies, and the one-launch year would not be the same discrete map (round-3 ADVICE) -- launch by launch then
@@ -782,8 +511,8 @@ static bool frozen_eligible(const nk2d_ctx* c, const double* sched, int64_t n) {
     // (one to four levels per lane; five to eight with linear sources -- for the file-driven forced module there with option
     // "frozen_forced": bit 1 without, bit 2 with a sink threshold)
     if (c->E > c->frozen_persistent_max_e || c->E > 8) return false;
-    if (c->E > 4 && c->kind != 0 && !(c->kind == 2 && (c->frozen_forced & (thres ? 2 : 1)))) return false;
-    if (thres) {
+    if (c->E > 4 && c->kind != 0 && !phos && !(c->kind == 2 && (c->frozen_forced & (thres ? 2 : 1)))) return false;
+    if (thres || phos) {
         // UPR is formed where the launch path evaluates the Jacobian anew (replay_rows): at a step start, or -- option
         // "jac_stage_state" -- at a stage time of the row's own attempt.  A schedule it would refuse goes to it, to be refused
         const double RCs[3] = {0.15505102572168222, 0.6449489742783178, 1.0};
@@ -814,7 +543,7 @@ static bool frozen_eligible(const nk2d_ctx* c, const double* sched, int64_t n) {
 // (the device is not asked again every year); "frozen_cache_gb" is looked at every time.
 static int frozen_form(nk2d_ctx* c, int64_t n, uint64_t key_full, bool* lean) {
     *lean = c->frozen_cache_lean == 1;
-    if (frozen_thres(c)) { *lean = true; return 0; }    // (eligible with a lean cache only: "frozen_cache_lean" 2 always means lean here)
+    if (frozen_thres(c) || c->kind == 1) { *lean = true; return 0; }    // (eligible with a lean cache only: "frozen_cache_lean" 2 always means lean here)
     if (c->frozen_cache_lean != 2) return 0;
     const nk2d_frozen_cache* fc = (const nk2d_frozen_cache*)c->frozen_cache;
     if (fc && fc->alloc_state.load() != 0) { *lean = fc->alloc_lean; return 0; }
@@ -866,6 +595,31 @@ int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
     return 0;
 }
 
+// what lives in LDS (option "frozen_coef_lds", bits of LdsSrc) and which columns share a workgroup (option "frozen_by_column"):
+// as much as lets a compute unit hold what the grid needs of it -- ceil(waves / compute units) waves: pivots, then the step
+// block, then W are given up until it fits the 160 KB (E = 8 keeps everything but the pivots)
+static int frozen_lds_shape(nk2d_ctx* c, bool phos, int* coef_lds_out, int* by_column_out) {
+    int coef_lds = (c->E >= 3) ? c->frozen_coef_lds : 0;
+    // (by column -- and with it the step block and the pivots -- from five levels per lane: 416^2 125.2 -> 120.3 ms; at four the shared
+    // block does not pay for the wider hand-over, 208^2 65.2 -> 68.1 ms: profiles/r04_frozen_lds_by_column.log; option value 2 forces it)
+    int by_column = (c->frozen_by_column && c->tc <= NK2D_WAVES_PER_BLOCK && coef_lds &&
+                     (c->E >= 5 || (c->frozen_by_column >= 2 && c->E >= 3))) ? 1 : 0;
+    // (phosphorus: its tracers are coupled inside a ypos column -- by column whatever the two options say, "frozen_coef_lds" 0 included)
+    if (phos) by_column = 1;
+    if (!by_column) coef_lds &= 3;
+    hipDeviceProp_t prop;
+    NK2D_CHECK(c, hipGetDeviceProperties(&prop, c->dev));
+    const int nw = by_column ? c->tc : std::max(1, std::min(NK2D_WAVES_PER_BLOCK, c->frozen_wpb));
+    const int wgs = by_column ? c->ny : (c->ncol + nw - 1) / nw;
+    const int per_cu = (wgs + prop.multiProcessorCount - 1) / prop.multiProcessorCount;
+    for (const int drop : {8, 4, 2}) {
+        if (8 * frozen_lds_doubles(c->E, coef_lds, by_column != 0, nw) * (size_t)per_cu <= 160u * 1024u) break;
+        coef_lds &= ~drop;
+    }
+    *coef_lds_out = coef_lds; *by_column_out = by_column;
+    return 0;
+}
+
 // (Asking for that slab EARLIER -- at the end of the free-running year whose steps the products will repeat, so that it is
 // there when the first product comes -- was built and measured in round 4 and taken out again: in a fresh process the
 // hipMalloc of 120 GB holds the driver for ~ 4 s, and the preconditioner's set-up, which lies between F(x) and the first
@@ -883,10 +637,27 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     NK2D_TRY(frozen_form(c, n, key_full, &want_lean));
     // (a thresholded forced module -- eligible with option "frozen_forced" bit 2 only, and lean: a row holds its source plane too)
     const bool want_src = frozen_thres(c);
+    // (phosphorus -- eligible with option "frozen_phosphorus" only, and lean: a row is KV and J, the light plane is the context's own)
+    const bool want_phos = c->kind == 1;
     const size_t per_row = frozen_row_doubles(c, want_lean, want_src);
     const size_t B = want_pieces ? frozen_piece_rows(c, want_lean, want_src) : 0, need = want_pieces ? ((size_t)n + B - 1) / B : 0;
     const double bytes = want_pieces ? 8.0 * (double)need * (double)B * (double)per_row : 8.0 * (double)n * (double)per_row;
     if (bytes > c->frozen_cache_max_gb * 1.0e9) return 1;
+    if (want_phos) {
+        // whether the chip holds the grid is known before anything is allocated or built (416 ypos columns at one wave per SIMD are
+        // the expected case that it does not): the occupancy check of the launch, asked ahead, for the flavours the option's value allows
+        FrozenPieceArgs A0 = {};
+        NK2D_TRY(frozen_lds_shape(c, true, &A0.coef_lds, &A0.by_column));
+        DevP P0 = make_devp(c);
+        const bool has_w2 = c->E >= 5;
+        auto fits = [&](bool w2) {
+            return want_pieces ? launch_frozen_phos<1>(c, P0, A0, w2, true) : launch_frozen_phos<0>(c, P0, static_cast<FrozenArgs&>(A0), w2, true);
+        };
+        hipError_t rc = fits(has_w2 && c->frozen_phosphorus == 3);
+        if (rc == hipErrorCooperativeLaunchTooLarge && has_w2 && c->frozen_phosphorus == 2) rc = fits(true);
+        if (rc == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return 1; }
+        NK2D_CHECK(c, rc);
+    }
     {   // what a thread was asked for: not there yet (launch by launch), there (adopt it), or refused (never again)
         const int st = frozen_adopt(c, (nk2d_frozen_cache*)c->frozen_cache);
         if (st == 1) return 1;
@@ -924,7 +695,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     nk2d_frozen_cache* fc = (nk2d_frozen_cache*)c->frozen_cache;
     if (!fc) { fc = new nk2d_frozen_cache(); c->frozen_cache = fc; }
     // (the rows also say which steps carry an error estimate)
-    const uint64_t key = key_full ^ (want_lean ? FROZEN_LEAN_KEY : 0) ^ (want_src ? FROZEN_SRC_KEY : 0);
+    const uint64_t key = key_full ^ (want_lean ? FROZEN_LEAN_KEY : 0) ^ (want_src ? FROZEN_SRC_KEY : 0) ^ (want_phos ? FROZEN_PHOS_KEY : 0);
     if (fc->key != key || fc->n != n) {
         // option "frozen_cache_after": that many years of a schedule run launch by launch before its cache is built.  Default
         // 0; -1: 0 for caches below 8 GB, 3 above.  Building a 100 GB cache takes 26 ms where a one-launch year saves 40
@@ -945,13 +716,14 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             NK2D_CHECK(c, hipMalloc((void**)&fc->lean_tab, sizeof(double) * (3 * c->nv + 3 * ntab)));
             fc->lean_tab_doubles = 3 * c->nv + 3 * ntab;
         }
-        if (want_src && fc->upr_doubles < c->nv) {
-            // the plane the year's kernel forms UPR in: allocated once
+        if ((want_src || want_phos) && fc->upr_doubles < (want_phos ? c->np : c->nv)) {
+            // the plane the year's kernel forms UPR in: allocated once (phosphorus: one plane, d uptake / d po4)
+            const size_t upr_doubles = want_phos ? c->np : c->nv;
             NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
             if (fc->upr) (void)hipFree(fc->upr);
             fc->upr = nullptr; fc->upr_doubles = 0;
-            NK2D_CHECK(c, hipMalloc((void**)&fc->upr, sizeof(double) * c->nv));
-            fc->upr_doubles = c->nv;
+            NK2D_CHECK(c, hipMalloc((void**)&fc->upr, sizeof(double) * upr_doubles));
+            fc->upr_doubles = upr_doubles;
         }
         if (want_pieces) {
             if (fc->pieces.size() < need) {
@@ -1174,29 +946,12 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     A.spin_ticks = (long long)(c->barrier_timeout_ms * 1.0e5);
     A.fences = c->year_fences;
     // a thresholded forced module: the year forms UPR, in the cache's own plane, from the rows' source planes
-    A.upr_on = want_src ? 1 : 0;
+    // (phosphorus: from the state and the context's light plane alone.  A year that is handed back leaves the context's own UPR what the
+    // launch path left there)
+    A.upr_on = (want_src || want_phos) ? 1 : 0;
     A.SRC = (want_src && !want_pieces) ? fc->C.J + fc->cap_rows * 5 * c->np : nullptr;
-    if (want_src) P.UPR = fc->upr;
-    // what lives in LDS (option "frozen_coef_lds", bits of LdsSrc) and which columns share a workgroup (option "frozen_by_column"):
-    // as much as lets a compute unit hold what the grid needs of it -- ceil(waves / compute units) waves: pivots, then the step
-    // block, then W are given up until it fits the 160 KB (E = 8 keeps everything but the pivots)
-    A.coef_lds = (c->E >= 3) ? c->frozen_coef_lds : 0;
-    // (by column -- and with it the step block and the pivots -- from five levels per lane: 416^2 125.2 -> 120.3 ms; at four the shared
-    // block does not pay for the wider hand-over, 208^2 65.2 -> 68.1 ms: profiles/r04_frozen_lds_by_column.log; option value 2 forces it)
-    A.by_column = (c->frozen_by_column && c->tc <= NK2D_WAVES_PER_BLOCK && A.coef_lds &&
-                   (c->E >= 5 || (c->frozen_by_column >= 2 && c->E >= 3))) ? 1 : 0;
-    if (!A.by_column) A.coef_lds &= 3;
-    {
-        hipDeviceProp_t prop;
-        NK2D_CHECK(c, hipGetDeviceProperties(&prop, c->dev));
-        const int nw = A.by_column ? c->tc : std::max(1, std::min(NK2D_WAVES_PER_BLOCK, c->frozen_wpb));
-        const int wgs = A.by_column ? c->ny : (c->ncol + nw - 1) / nw;
-        const int per_cu = (wgs + prop.multiProcessorCount - 1) / prop.multiProcessorCount;
-        for (const int drop : {8, 4, 2}) {
-            if (8 * frozen_lds_doubles(c->E, A.coef_lds, A.by_column != 0, nw) * (size_t)per_cu <= 160u * 1024u) break;
-            A.coef_lds &= ~drop;
-        }
-    }
+    if (want_src || want_phos) P.UPR = fc->upr;
+    NK2D_TRY(frozen_lds_shape(c, want_phos, &A.coef_lds, &A.by_column));
     // option "frozen_team": a workgroup per column (four waves: newton_team_body) instead of a wave per column, up to two levels per
     // lane.  Measured in round 3 (profiles/r03_frozen_team.log, r03_frozen_nbsync.log): teams want a CU each and beat the
     // wave-per-column year at every such size -- 26^2 9.4 ms, 52^2 14.9, 104^2 27.0 with the neighbour hand-over.
@@ -1214,7 +969,24 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
             explicit Turn(int w) : waves(w) { nk2d_turn_take(waves); }
             ~Turn() { nk2d_turn_give(waves); }
         } turn(team ? 4 * c->ncol : c->ncol);
-        if (want_lean) rc = want_pieces ? launch_frozen<1, 1>(c, team, dim3(nblk), P, A) : launch_frozen<0, 1>(c, team, dim3(nblk), P, static_cast<FrozenArgs&>(A));
+        c->frozen_two_waves_last = 0;
+        if (want_phos) {
+            // option "frozen_phosphorus": 1 the flavour of one wave per SIMD, where the chip holds its grid; 2 where it does not, the
+            // 256-register flavour, if the chip holds that one; 3 the 256-register flavour wherever it exists (five to eight levels per lane)
+            const bool has_w2 = c->E >= 5;
+            bool two = has_w2 && c->frozen_phosphorus == 3;
+            auto go = [&](bool w2) {
+                return want_pieces ? launch_frozen_phos<1>(c, P, A, w2) : launch_frozen_phos<0>(c, P, static_cast<FrozenArgs&>(A), w2);
+            };
+            rc = go(two);
+            if (rc == hipErrorCooperativeLaunchTooLarge && !two && has_w2 && c->frozen_phosphorus == 2) {
+                (void)hipGetLastError();
+                two = true;
+                rc = go(two);
+            }
+            c->frozen_two_waves_last = two ? 1 : 0;
+        }
+        else if (want_lean) rc = want_pieces ? launch_frozen<1, 1>(c, team, dim3(nblk), P, A) : launch_frozen<0, 1>(c, team, dim3(nblk), P, static_cast<FrozenArgs&>(A));
         else rc = want_pieces ? launch_frozen<1, 0>(c, team, dim3(nblk), P, A) : launch_frozen<0, 0>(c, team, dim3(nblk), P, static_cast<FrozenArgs&>(A));
         if (rc == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return 1; }
         NK2D_CHECK(c, rc);

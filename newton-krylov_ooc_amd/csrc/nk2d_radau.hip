@@ -1167,11 +1167,18 @@ int run_replay(Ctl& s, const double* sched, int64_t n, bool check) {
                 if (nk2d_frozen_cache_is_lean(c)) c->frozen_lean_years++;
                 // (a file-driven forced module above four levels per lane, or with a thresholded sink: option "frozen_forced" let it in)
                 if (c->kind == 2 && (c->E > 4 || (c->d.sms_nrec > 0 && c->d.sink_thres > 0.0))) c->frozen_forced_years++;
+                // (phosphorus: option "frozen_phosphorus" let it in; of those years, the ones that ran the 256-register flavour)
+                if (c->kind == 1) { c->frozen_phosphorus_years++; c->frozen_two_waves_years += c->frozen_two_waves_last; }
                 return 0;
             }
             return 3;
         }
-        if (prc == 2) { c->st.nbarrier_timeouts++; return 3; }
+        if (prc == 2) {
+            c->st.nbarrier_timeouts++;
+            // (a one-launch year of option "frozen_phosphorus" that is handed back is also booked where its user looks for years given up)
+            if (c->kind == 1) c->frozen_fallbacks++;
+            return 3;
+        }
     }
     int64_t start = 0;
     std::vector<char> err_done((size_t)n, 0);

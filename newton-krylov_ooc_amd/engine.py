@@ -227,6 +227,10 @@ class ModuleEngine:
         # eight levels per lane, bit 2 a thresholded sink on the lean cache (csrc/nk2d_frozen.hip)
         if "NK2D_FROZEN_FORCED" in os.environ:
             self.set_option("frozen_forced", float(os.environ["NK2D_FROZEN_FORCED"]))
+        # the one-launch frozen year for the phosphorus module, on the lean cache at three to eight levels per lane: 1 one wave per SIMD,
+        # 2 the 256-register flavour where that one is not resident, 3 that flavour wherever it exists (csrc/nk2d_frozen.hip)
+        if "NK2D_FROZEN_PHOSPHORUS" in os.environ:
+            self.set_option("frozen_phosphorus", float(os.environ["NK2D_FROZEN_PHOSPHORUS"]))
         # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_TWO_ENDED" in os.environ:
             self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
