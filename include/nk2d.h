@@ -258,6 +258,7 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    "frozen_cache_pieces" (pieces held; "frozen_cache_bytes" is then their sum), "frozen_cache_piece_allocs" (pieces allocated
    so far), "frozen_cache_early_requests" (early requests made), "frozen_cache_lean" (1 while the cache held is lean),
    "frozen_lean_years" (one-launch years run on a lean cache; also counted in "frozen_persistent_years"),
+   "frozen_lds_bits" (the bits of option "frozen_coef_lds" in effect in the one-launch year launched last, after fitting),
    "frozen_forced_years" (one-launch years only option "frozen_forced" made possible; also counted in "frozen_persistent_years",
    and in "frozen_lean_years" where lean),
    "frozen_phosphorus_years" (one-launch years of the phosphorus module, option "frozen_phosphorus"; also counted in
@@ -457,9 +458,13 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    "frozen_team" (1, default: a four-wave team per column inside that launch up to two levels per lane; 0: a wave per
    column), "frozen_wpb" (columns per workgroup of the wave-per-column
    flavour with that hand-over, 1 .. 4, default 2: the waves of a workgroup move in lock step, a neighbour in another
-   workgroup is read over the fabric), "frozen_coef_lds" (bits, default 15: what a wave of that flavour keeps in LDS for the
-   year at three and more levels per lane -- 1 the static coefficients of its column, 2 W, 4 the step's mixing columns and
-   vertical Jacobian diagonals, 8 the real system's pivots; bits 4 and 8 need "frozen_by_column"), "frozen_by_column" (1,
+   workgroup is read over the fabric), "frozen_coef_lds" (bits, default 63: what a wave of that flavour keeps on its compute unit
+   for the year at three and more levels per lane -- 1 the static coefficients of its column, 2 W, 4 the step's mixing columns and
+   vertical Jacobian diagonals, 8 the real system's pivots, 16 the column's own state Y, all of them in LDS, and 32 the column's
+   own three stage values in registers from one Newton phase to the next; bits 4 and 8 need "frozen_by_column"; bits 16 and 32
+   exist on top of the other four, on the full cache, at five to seven levels per lane -- a cache in pieces has 32 only together
+   with 16 --; what does not fit the compute unit's LDS is given up, 16 first: counter "frozen_lds_bits" is the set the year
+   launched last ran with), "frozen_by_column" (1,
    default: from five levels per lane a workgroup is ONE ypos column with all its tracers, so that what is the same for every
    tracer of a column is shared through LDS; 2: from three levels per lane; 0: adjacent columns of one tracer),
    "hook_spec_depth" (1 or 2, default 2: whole Newton iterations a controller with a vector norm hook queues ahead of a verdict), "barrier_timeout_ms" (longest wait at a grid barrier of the one-launch years, default 2000:

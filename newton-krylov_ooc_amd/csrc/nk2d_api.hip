@@ -183,7 +183,7 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
     if (key == "year_fences") { c->year_fences = value != 0.0; return 0; }
     if (key == "frozen_persistent") { c->frozen_persistent = value != 0.0; return 0; }
     if (key == "frozen_team") { c->frozen_team = value != 0.0; return 0; }
-    if (key == "frozen_coef_lds") { c->frozen_coef_lds = (int)value & 15; return 0; }
+    if (key == "frozen_coef_lds") { c->frozen_coef_lds = (int)value & 63; return 0; }
     if (key == "frozen_by_column") { c->frozen_by_column = (int)value; return 0; }
     if (key == "frozen_cache_after") { c->frozen_cache_after = (int)value; return 0; }
     if (key == "spec_bias") { c->spec_bias = value > 0.0 ? value : 1.0; return 0; }
@@ -624,7 +624,8 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_two_waves_last = 0;
     c->frozen_phosphorus_years = c->frozen_two_waves_years = 0;
     c->frozen_cache_piece_allocs = c->frozen_cache_early_requests = 0;
-    c->frozen_coef_lds = 15;
+    c->frozen_coef_lds = 63;
+    c->frozen_lds_bits = 0;
     c->frozen_by_column = 1;
     c->strm = nullptr;
     c->spec_bias = 1.0;
@@ -1167,6 +1168,7 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_cache_bytes") v = nk2d_frozen_cache_bytes(c);
     else if (key == "frozen_cache_pieces") v = nk2d_frozen_cache_npieces(c);
     else if (key == "frozen_cache_lean") v = nk2d_frozen_cache_is_lean(c);
+    else if (key == "frozen_lds_bits") v = c->frozen_lds_bits;
     else if (key == "frozen_lean_years") v = c->frozen_lean_years;
     else if (key == "frozen_forced_years") v = c->frozen_forced_years;
     else if (key == "frozen_phosphorus_years") v = c->frozen_phosphorus_years;

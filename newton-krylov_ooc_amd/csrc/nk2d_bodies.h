@@ -888,11 +888,25 @@ __device__ __forceinline__ void w_lds_put(double* s, int r, int lane, const doub
 //   bit 2  step: what is constant over the Newton iterations of a STEP and the same for every tracer of the ypos column -- the
 //                three mixing columns of the stage times, then the vertical Jacobian diagonals JL, JU ([5][E][64] doubles)
 //   bit 3  piv : the pivot reciprocals of the column's real system ([E][64])
+//   bit 4  y   : the column's own state Y ([E][64]): it changes once per step, and the wave that reads it writes it (OwnState)
+// and, no LDS at all,
+//   bit 5  z   : the column's own three stage values stay in the wave's registers from the update part of one phase to the
+//                stage part of the next (OwnState::z)
 struct LdsSrc {
     const double* coef;
     double* w;
     const double* step;
     const double* piv;
+    double* y;
+};
+// What a wave of the one-launch year carries of its own column from phase to phase (CL bits 4, 5).  Every value in it is also
+// stored where it always was -- the neighbours, the error estimate and the host read it there --; the wave itself no longer
+// fetches back what it has just computed.  `valid` (wave-uniform) is 0 at the start of the year and behind a phase that
+// wrote Z or Y by another path: the next stage part then loads both from memory and refills the LDS copy of Y.
+template <int E>
+struct OwnState {
+    double z[3][E];
+    int valid;
 };
 template <int E>
 __device__ __forceinline__ void col_lds_get(const double* s, int r, int lane, double (&v)[E]) {
@@ -901,7 +915,8 @@ __device__ __forceinline__ void col_lds_get(const double* s, int r, int lane, do
 }
 template <int E, int KIND, int FACTOR, int STAGE, int MP = 0, int FINAL = 0, int CL = 0>
 __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs& A, int task, int lane,
-                                                  const FinalArgs* fin = nullptr, const LdsSrc* lds = nullptr) {
+                                                  const FinalArgs* fin = nullptr, const LdsSrc* lds = nullptr,
+                                                  OwnState<E>* own = nullptr) {
     const double* coef_lds = (CL & 1) ? lds->coef : nullptr;
     double* w_lds = (CL & 2) ? lds->w : nullptr;
     (void)coef_lds; (void)w_lds;
@@ -913,7 +928,16 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         if constexpr (CL & 1) load_coef_lds<E>(coef_lds, lane, cf);       // (the wave's own column: stored there at kernel entry)
         else load_coef<E>(P, j, lane, cf);
         double y0[E], ys[E], yn[E];
-        load_col<E, MP>(A.st.y, task, lane, y0);
+        if constexpr (CL & 16) {
+            if (!own->valid) {      // (Y was written by another path: from memory, and into the LDS copy)
+                load_col<E, MP>(A.st.y, task, lane, y0);
+                w_lds_put<E>(lds->y, 0, lane, y0);
+            } else {
+                col_lds_get<E>(lds->y, 0, lane, y0);
+            }
+        } else {
+            load_col<E, MP>(A.st.y, task, lane, y0);
+        }
         load_col<E, MP>(A.st.y, cs_col, lane, ys);
         load_col<E, MP>(A.st.y, cn_col, lane, yn);
 #pragma unroll
@@ -921,7 +945,16 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             double c[E], cs[E], cn[E], kv[E], f[E];
-            load_col<E, MP>(A.st.z + i * A.st.nv, task, lane, c);
+            if constexpr (CL & 32) {
+                if (own->valid) {   // (what the update part of the phase before stored to A.st.z for the others)
+#pragma unroll
+                    for (int e = 0; e < E; ++e) c[e] = own->z[i][e];
+                } else {
+                    load_col<E, MP>(A.st.z + i * A.st.nv, task, lane, c);
+                }
+            } else {
+                load_col<E, MP>(A.st.z + i * A.st.nv, task, lane, c);
+            }
             load_col<E, MP>(A.st.z + i * A.st.nv, cs_col, lane, cs);
             load_col<E, MP>(A.st.z + i * A.st.nv, cn_col, lane, cn);
             if constexpr (CL & 4) col_lds_get<E>(lds->step, i, lane, kv);
@@ -1104,11 +1137,26 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         store_col<E, MP>(A.sw.xr_new, task, lane, fr);
         store_col<E, MP>(A.sw.xcr_new, task, lane, fcr);
         store_col<E, MP>(A.sw.xci_new, task, lane, fci);
+        if constexpr (CL & 32) {
+            // (the update part of the iteration's last phase rewrites the stage values: nothing to keep through its solves)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) own->z[i][e] = 0.0;
+            }
+            own->valid = 0;
+        }
         return;
     }
-    // dW = (fr, fcr, fci): norm partial, W += dW, Z = T W
+    // dW = (fr, fcr, fci): norm partial, W += dW, Z = T W.  A caller that reads the partial of this iteration nowhere (the
+    // one-launch year knows the last two iterations of a step) passes no place for it: the scale, the divisions, the sum over
+    // the wave and -- where the end of the step does not need it -- the state column are then left out
+    const bool norm = A.part != nullptr;
     double yy[E], w0[E], w1[E], w2[E];
-    load_col<E, MP>(A.st.y, task, lane, yy);
+    if (FINAL || norm) {
+        if constexpr (CL & 16) col_lds_get<E>(lds->y, 0, lane, yy);
+        else load_col<E, MP>(A.st.y, task, lane, yy);
+    }
     if constexpr (CL & 2) {
         w_lds_get<E>(w_lds, 0, lane, w0); w_lds_get<E>(w_lds, 1, lane, w1); w_lds_get<E>(w_lds, 2, lane, w2);
     } else {
@@ -1116,18 +1164,23 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         load_col<E>(A.st.w + A.st.nv, task, lane, w1);
         load_col<E>(A.st.w + 2 * A.st.nv, task, lane, w2);
     }
-    double acc = 0.0;
+    if (norm) {
+        double acc = 0.0;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const double sc = P.atol + fabs(yy[e]) * P.rtol;
+            const double d0 = fr[e] / sc, d1 = fcr[e] / sc, d2 = fci[e] / sc;
+            acc += (d0 * d0 + d1 * d1) + d2 * d2;
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) st_mp<MP>(A.part + task, acc);
+    }
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-        const double sc = P.atol + fabs(yy[e]) * P.rtol;
-        const double d0 = fr[e] / sc, d1 = fcr[e] / sc, d2 = fci[e] / sc;
-        acc += (d0 * d0 + d1 * d1) + d2 * d2;
         w0[e] = w0[e] + fr[e];
         w1[e] = w1[e] + fcr[e];
         w2[e] = w2[e] + fci[e];
     }
-    acc = wave_sum(acc);
-    if (lane == 0) st_mp<MP>(A.part + task, acc);
     double* wout = const_cast<double*>(A.st.w);
     if constexpr (FINAL) {
         // end of a frozen step (FinalArgs): the operations of commit_tend_body (y_new) and predict_body, on registers
@@ -1140,6 +1193,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
             yn[e] = yy[e] + z2[e];
         }
         store_col<E, MP>(fin->ynew, task, lane, yn);
+        if constexpr (CL & 16) w_lds_put<E>(lds->y, 0, lane, yn);      // (the buffer that becomes Y: so does the copy)
         const double xs[3] = {fin->x0, fin->x1, fin->x2};
         double o[3][E];
 #pragma unroll
@@ -1165,6 +1219,14 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
             if constexpr (CL & 2) w_lds_put<E>(w_lds, r, lane, wv);
             else store_col<E>(wout + r * A.st.nv, task, lane, wv);
         }
+        if constexpr (CL & 32) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) own->z[i][e] = o[i][e];
+            }
+        }
+        if constexpr ((CL & 48) != 0) own->valid = 1;
         return;
     }
     double* zout = A.st.zout;
@@ -1181,7 +1243,12 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
 #pragma unroll
         for (int e = 0; e < E; ++e) zz[e] = (cT[r][0] * w0[e] + cT[r][1] * w1[e]) + cT[r][2] * w2[e];
         store_col<E, MP>(zout + r * A.st.nv, task, lane, zz);
+        if constexpr (CL & 32) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) own->z[r][e] = zz[e];
+        }
     }
+    if constexpr ((CL & 48) != 0) own->valid = 1;
 }
 
 
@@ -2226,7 +2293,7 @@ struct FrozenRow {
 struct FrozenArgs {
     double *Y, *YOLD, *Z, *ZN, *W, *F;
     double *BR, *BCR, *BCI, *XR[2], *XCR[2], *XCI[2];
-    double* PART;                // scratch partials [ncol]
+    double* PART;                // scratch partials [ncol] (teams, and one and two levels per lane: the wave-per-column body forms only partials that are read)
     double* STEP_PART;           // rows of ncol: 3 per step (last iteration, the one before, error estimate -- unused here)
     const FrozenRow* rows;
     CachePtrs C;
@@ -2236,7 +2303,8 @@ struct FrozenArgs {
     double* out;                 // [32]: status, rows done, parities
     long long spin_ticks;
     int fences;
-    int coef_lds;                // option "frozen_coef_lds" (bits of LdsSrc): what a wave finds in LDS; bits 2, 3 need `by_column`
+    int coef_lds;                // option "frozen_coef_lds" (bits of LdsSrc) as frozen_lds_shape() fitted it: what a wave finds in LDS (bits 2, 3, 4
+                                 // need `by_column`) and, bit 5, keeps in registers
     int by_column;               // 1: a workgroup is ONE ypos column with all its tracers (a wave each) instead of adjacent columns of one tracer
     // option "frozen_forced" bit 2 (forced module with a thresholded sink, lean cache): the rows' file-source planes at their Jacobian
     // times, [n][np] behind J in the slab (a cache in pieces: PieceTab::oS), and 1 where the year forms UPR from them

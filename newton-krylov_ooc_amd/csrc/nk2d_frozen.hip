@@ -116,6 +116,11 @@ __device__ __forceinline__ void frozen_factor_phase(const DevP& P, const FusedAr
 // from five levels per lane -- k_frozen_persistent_w2, the same within 256 registers (as k_stream has k_stream_w2).  Included text
 // rather than a device function called by both: through a function the instantiations of k_frozen_persistent came out with
 // other register counts (1 to 14 vector registers up or down on 38 of 80); as text they are what they were.
+// A column's own state from phase to phase (OwnState, bits 16 and 32 of option "frozen_coef_lds"): the instantiations that carry it.
+// A wave per column by column, the linear-source kinds, the full cache, five to seven levels per lane: the lean factorising
+// phase and phosphorus keep their bodies, and at eight levels per lane neither the registers (421 of 512 before, one of them
+// spilled) nor the LDS of a compute unit with two workgroups hold it (profiles/r09_frozen_own_state_resources.log)
+#define NK2D_FROZEN_OWN(E, KIND, TEAM, LEAN) ((E) >= 5 && (E) <= 7 && ((KIND) == 0 || (KIND) == 2) && !(TEAM) && !(LEAN))
 template <int E, int KIND, int TEAM = 0, int PIECES = 0, int LEAN = 0>
 __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typename FrozenArgOf<PIECES>::type A) {
 #include "nk2d_frozen_body.inc"
@@ -330,7 +335,8 @@ void nk2d_frozen_cache_free(nk2d_ctx* c) {
 static size_t frozen_lds_doubles(int E, int bits, bool by_column, int nwaves) {
     if (!bits) return 0;
     if (!by_column) return (size_t)nwaves * (NK2D_COEF_LDS_DOUBLES(E) + ((bits & 2) ? 3 * E * 64 : 0));
-    return NK2D_COEF_LDS_DOUBLES(E) + ((bits & 4) ? 5 * E * 64 : 0) + (size_t)nwaves * (((bits & 2) ? 3 * E * 64 : 0) + ((bits & 8) ? E * 64 : 0));
+    return NK2D_COEF_LDS_DOUBLES(E) + ((bits & 4) ? 5 * E * 64 : 0) +
+           (size_t)nwaves * (((bits & 2) ? 3 * E * 64 : 0) + ((bits & 8) ? E * 64 : 0) + ((bits & 16) ? E * 64 : 0));
 }
 
 template <class K, class ARGS>
@@ -597,8 +603,11 @@ int nk2d_frozen_cache_early(nk2d_ctx* c, const double* sched, int64_t n) {
 
 // what lives in LDS (option "frozen_coef_lds", bits of LdsSrc) and which columns share a workgroup (option "frozen_by_column"):
 // as much as lets a compute unit hold what the grid needs of it -- ceil(waves / compute units) waves: pivots, then the step
-// block, then W are given up until it fits the 160 KB (E = 8 keeps everything but the pivots)
-static int frozen_lds_shape(nk2d_ctx* c, bool phos, int* coef_lds_out, int* by_column_out) {
+// block, then W are given up until it fits the 160 KB (E = 8 keeps everything but the pivots).  The column's own state (bits 16:
+// Y in LDS, given up before anything else, and 32: the stage values in registers) exists in the instantiations
+// NK2D_FROZEN_OWN names, by column, on top of everything else: with a part of 15 missing both bits go; a cache in pieces has
+// the stage values only together with Y
+static int frozen_lds_shape(nk2d_ctx* c, bool phos, bool lean, bool pieces, int* coef_lds_out, int* by_column_out) {
     int coef_lds = (c->E >= 3) ? c->frozen_coef_lds : 0;
     // (by column -- and with it the step block and the pivots -- from five levels per lane: 416^2 125.2 -> 120.3 ms; at four the shared
     // block does not pay for the wider hand-over, 208^2 65.2 -> 68.1 ms: profiles/r04_frozen_lds_by_column.log; option value 2 forces it)
@@ -607,15 +616,19 @@ static int frozen_lds_shape(nk2d_ctx* c, bool phos, int* coef_lds_out, int* by_c
     // (phosphorus: its tracers are coupled inside a ypos column -- by column whatever the two options say, "frozen_coef_lds" 0 included)
     if (phos) by_column = 1;
     if (!by_column) coef_lds &= 3;
+    const bool team = c->frozen_team && c->E <= 2;
+    if (!by_column || phos || (coef_lds & 15) != 15 || !NK2D_FROZEN_OWN(c->E, c->kind, team, lean)) coef_lds &= 15;
     hipDeviceProp_t prop;
     NK2D_CHECK(c, hipGetDeviceProperties(&prop, c->dev));
     const int nw = by_column ? c->tc : std::max(1, std::min(NK2D_WAVES_PER_BLOCK, c->frozen_wpb));
     const int wgs = by_column ? c->ny : (c->ncol + nw - 1) / nw;
     const int per_cu = (wgs + prop.multiProcessorCount - 1) / prop.multiProcessorCount;
-    for (const int drop : {8, 4, 2}) {
+    for (const int drop : {16, 8, 4, 2}) {
         if (8 * frozen_lds_doubles(c->E, coef_lds, by_column != 0, nw) * (size_t)per_cu <= 160u * 1024u) break;
         coef_lds &= ~drop;
     }
+    if ((coef_lds & 15) != 15) coef_lds &= 15;
+    if (pieces && (coef_lds & 48) == 32) coef_lds &= 15;      // (the piece flavour has no body for the stage values without Y)
     *coef_lds_out = coef_lds; *by_column_out = by_column;
     return 0;
 }
@@ -647,7 +660,7 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
         // whether the chip holds the grid is known before anything is allocated or built (416 ypos columns at one wave per SIMD are
         // the expected case that it does not): the occupancy check of the launch, asked ahead, for the flavours the option's value allows
         FrozenPieceArgs A0 = {};
-        NK2D_TRY(frozen_lds_shape(c, true, &A0.coef_lds, &A0.by_column));
+        NK2D_TRY(frozen_lds_shape(c, true, true, want_pieces, &A0.coef_lds, &A0.by_column));
         DevP P0 = make_devp(c);
         const bool has_w2 = c->E >= 5;
         auto fits = [&](bool w2) {
@@ -951,7 +964,8 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     A.upr_on = (want_src || want_phos) ? 1 : 0;
     A.SRC = (want_src && !want_pieces) ? fc->C.J + fc->cap_rows * 5 * c->np : nullptr;
     if (want_src || want_phos) P.UPR = fc->upr;
-    NK2D_TRY(frozen_lds_shape(c, want_phos, &A.coef_lds, &A.by_column));
+    NK2D_TRY(frozen_lds_shape(c, want_phos, want_lean, want_pieces, &A.coef_lds, &A.by_column));
+    c->frozen_lds_bits = A.coef_lds;
     // option "frozen_team": a workgroup per column (four waves: newton_team_body) instead of a wave per column, up to two levels per
     // lane.  Measured in round 3 (profiles/r03_frozen_team.log, r03_frozen_nbsync.log): teams want a CU each and beat the
     // wave-per-column year at every such size -- 26^2 9.4 ms, 52^2 14.9, 104^2 27.0 with the neighbour hand-over.

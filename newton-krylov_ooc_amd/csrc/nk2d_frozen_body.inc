@@ -41,33 +41,57 @@
 #define FZ_ZN (swapZ ? A.Z : A.ZN)
 #define FZ_SYNC() \
     if (!nbs.sync()) { status = 1; goto finish; }
+    // behind a phase whose body does not carry the stage values: nothing of OwnState::z is kept through the next one's solves
+#define FZ_OWN_DEAD() \
+    if constexpr (OWN) { \
+        _Pragma("unroll") for (int r_ = 0; r_ < 3; ++r_) { \
+            _Pragma("unroll") for (int e_ = 0; e_ < E; ++e_) own.z[r_][e_] = 0.0; \
+        } \
+    }
     // a wave per column, three and more levels per lane (option "frozen_coef_lds"): the static coefficients of the wave's column
     // in LDS for the whole year (dynamic shared memory of the launch: NK2D_COEF_LDS_DOUBLES(E) doubles per wave)
     constexpr bool COEF_LDS = NB != 0 && !TEAM && !XCD && E >= 3;
     // Layout of the dynamic shared memory.  Adjacent columns: per wave [coefficients][W].  By column: [coefficients of the ypos
-    // column][step block: 3 mixing columns, JL, JU][per wave: W][per wave: pivots of the real system] (each part present where
-    // its bit of A.coef_lds is set; frozen_lds_doubles() on the host computes the same)
+    // column][step block: 3 mixing columns, JL, JU][per wave: W][per wave: pivots of the real system][per wave: own Y] (each part
+    // present where its bit of A.coef_lds is set; frozen_lds_doubles() on the host computes the same)
     extern __shared__ double dyn_lds[];
     const bool w_in_lds = COEF_LDS && (A.coef_lds & 2) != 0;
     const bool step_in_lds = COEF_LDS && by_col && (A.coef_lds & 4) != 0;
     const bool piv_in_lds = COEF_LDS && by_col && (A.coef_lds & 8) != 0;
+    // the column's own state from phase to phase (OwnState; bits 16, 32 of A.coef_lds -- the host sets them only on top of the
+    // full by-column set 15): Y in LDS, the stage values in registers.  Compiled in where the registers hold it; the piece
+    // flavour has the stage values only together with Y (with all three bodies <7, 0, 0, 1, 0> spills a register)
+    constexpr bool OWN = COEF_LDS && NK2D_FROZEN_OWN(E, KIND, TEAM, LEAN);
+    const int own_bits = OWN && by_col ? (A.coef_lds & 48) : 0;
+    (void)own_bits;
     const int nwv = (int)(blockDim.x >> 6);
     double* my_coef;
     double* my_w;
     double* step_lds = nullptr;
     double* my_piv = nullptr;
+    double* my_y = nullptr;
     if (by_col) {
         double* p = dyn_lds;
         my_coef = p; p += NK2D_COEF_LDS_DOUBLES(E);
         step_lds = p; p += step_in_lds ? 5 * E * 64 : 0;
         my_w = p + (size_t)tw * (3 * E * 64); p += w_in_lds ? (size_t)nwv * 3 * E * 64 : 0;
-        my_piv = p + (size_t)tw * (E * 64);
+        my_piv = p + (size_t)tw * (E * 64); p += piv_in_lds ? (size_t)nwv * E * 64 : 0;
+        my_y = p + (size_t)tw * (E * 64);
     } else {
         my_coef = dyn_lds + (size_t)(threadIdx.x >> 6) * (NK2D_COEF_LDS_DOUBLES(E) + (w_in_lds ? 3 * E * 64 : 0));
         my_w = my_coef + NK2D_COEF_LDS_DOUBLES(E);
     }
-    const LdsSrc L = {my_coef, my_w, step_lds, my_piv};
+    const LdsSrc L = {my_coef, my_w, step_lds, my_piv, my_y};
     (void)L;
+    OwnState<OWN ? E : 1> own;
+    own.valid = 0;      // (the year's first phase reads the state the host put there and the zeros stored below)
+    if constexpr (OWN) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) own.z[r][e] = 0.0;
+        }
+    }
     if constexpr (COEF_LDS) {
         if (A.coef_lds && col_wave && (!by_col || tw == 0)) {
             ColCoef<E> cf;
@@ -186,8 +210,12 @@
                 FA.sw.xr_new = src ? A.XR[0] : A.XR[1]; FA.sw.xcr_new = src ? A.XCR[0] : A.XCR[1];
                 FA.sw.xci_new = src ? A.XCI[0] : A.XCI[1];
                 FA.sw.first = first ? 1 : 0;
+                // (the year's check reads the norms of a step's last two iterations; the partials of the others went to a scratch
+                // row nobody read: the wave-per-column body no longer forms them.  The team and the one-wave bodies of one and two
+                // levels per lane keep the scratch row)
                 FA.part = (k == n_iter - 1) ? A.STEP_PART + (size_t)(3 * i) * P.ncol
-                                            : ((k == n_iter - 2) ? A.STEP_PART + (size_t)(3 * i + 1) * P.ncol : A.PART);
+                                            : ((k == n_iter - 2) ? A.STEP_PART + (size_t)(3 * i + 1) * P.ncol
+                                                                 : ((!TEAM && E >= 3) ? nullptr : A.PART));
                 FA.do_stage = do_stage ? 1 : 0; FA.do_update = do_update ? 1 : 0; FA.delta = delta ? 1 : 0;
                 if constexpr (COEF_LDS) {
                     if (step_in_lds && lds_step != i) {
@@ -233,13 +261,19 @@
                         if constexpr (KIND == 0 && E <= 2) {
                             if (m == 1) { newton_single_body<E, MPX, 1>(P, FA, wave, lane, &Fin); taken = true; }
                         }
-                        if constexpr (COEF_LDS) {
-                            if (step_in_lds && piv_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 15>(P, FA, wave, lane, &Fin, &L); taken = true; }
-                            else if (step_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 7>(P, FA, wave, lane, &Fin, &L); taken = true; }
-                            else if (w_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 3>(P, FA, wave, lane, &Fin, &L); taken = true; }
-                            else if (A.coef_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 1>(P, FA, wave, lane, &Fin, &L); taken = true; }
+                        if constexpr (OWN) {
+                            if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 63>(P, FA, wave, lane, &Fin, &L, &own); taken = true; }
+                            else if (!PIECES && own_bits == 32) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 47>(P, FA, wave, lane, &Fin, &L, &own); taken = true; }
+                            else if (own_bits == 16) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 31>(P, FA, wave, lane, &Fin, &L, &own); FZ_OWN_DEAD() taken = true; }
                         }
-                        if (!taken) newton_fused_body<E, KIND, 0, 1, MPX, 1>(P, FA, wave, lane, &Fin);
+                        if constexpr (COEF_LDS) {
+                            if (taken) {}
+                            else if (step_in_lds && piv_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 15>(P, FA, wave, lane, &Fin, &L); FZ_OWN_DEAD() taken = true; }
+                            else if (step_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 7>(P, FA, wave, lane, &Fin, &L); FZ_OWN_DEAD() taken = true; }
+                            else if (w_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 3>(P, FA, wave, lane, &Fin, &L); FZ_OWN_DEAD() taken = true; }
+                            else if (A.coef_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 1>(P, FA, wave, lane, &Fin, &L); FZ_OWN_DEAD() taken = true; }
+                        }
+                        if (!taken) { newton_fused_body<E, KIND, 0, 1, MPX, 1>(P, FA, wave, lane, &Fin); FZ_OWN_DEAD() }
                     }
                     swapY ^= 1;
                     if (do_stage) swapZ ^= 1;
@@ -259,13 +293,19 @@
                         if constexpr (KIND == 0 && E <= 2) {
                             if (m == 1) { newton_single_body<E, MPX, 0>(P, FA, wave, lane); taken = true; }
                         }
-                        if constexpr (COEF_LDS) {
-                            if (step_in_lds && piv_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 15>(P, FA, wave, lane, nullptr, &L); taken = true; }
-                            else if (step_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 7>(P, FA, wave, lane, nullptr, &L); taken = true; }
-                            else if (w_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 3>(P, FA, wave, lane, nullptr, &L); taken = true; }
-                            else if (A.coef_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 1>(P, FA, wave, lane, nullptr, &L); taken = true; }
+                        if constexpr (OWN) {
+                            if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 63>(P, FA, wave, lane, nullptr, &L, &own); taken = true; }
+                            else if (!PIECES && own_bits == 32) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 47>(P, FA, wave, lane, nullptr, &L, &own); taken = true; }
+                            else if (own_bits == 16) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 31>(P, FA, wave, lane, nullptr, &L, &own); FZ_OWN_DEAD() taken = true; }
                         }
-                        if (!taken) newton_fused_body<E, KIND, 0, 1, MPX, 0>(P, FA, wave, lane);
+                        if constexpr (COEF_LDS) {
+                            if (taken) {}
+                            else if (step_in_lds && piv_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 15>(P, FA, wave, lane, nullptr, &L); FZ_OWN_DEAD() taken = true; }
+                            else if (step_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 7>(P, FA, wave, lane, nullptr, &L); FZ_OWN_DEAD() taken = true; }
+                            else if (w_in_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 3>(P, FA, wave, lane, nullptr, &L); FZ_OWN_DEAD() taken = true; }
+                            else if (A.coef_lds) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 1>(P, FA, wave, lane, nullptr, &L); FZ_OWN_DEAD() taken = true; }
+                        }
+                        if (!taken) { newton_fused_body<E, KIND, 0, 1, MPX, 0>(P, FA, wave, lane); FZ_OWN_DEAD() }
                     }
                     if (do_stage && do_update) swapZ ^= 1;
                 }
@@ -293,6 +333,7 @@
                 Fin.x0 = R.x0; Fin.x1 = R.x1; Fin.x2 = R.x2;
                 Fin.nblk_cols = 0;
                 step_tail_body<E, MPX>(FZ_Y, FZ_Z, nv, Fin, A.W, wave, lane);
+                own.valid = 0;      // (this rare phase writes Y and Z: the next stage part takes both from memory)
                 if constexpr (COEF_LDS) {
                     if (w_in_lds) {     // (this rare phase writes W to memory: into the column's LDS copy from there)
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -329,6 +370,7 @@ finish:
         A.out[1] = (double)done; A.out[2] = (double)swapY; A.out[3] = (double)swapZ; A.out[4] = (double)nbs.phase;
     }
 #undef FZ_SYNC
+#undef FZ_OWN_DEAD
 #undef FZ_Y
 #undef FZ_YOLD
 #undef FZ_Z
