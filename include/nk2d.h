@@ -259,6 +259,9 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    so far), "frozen_cache_early_requests" (early requests made), "frozen_cache_lean" (1 while the cache held is lean),
    "frozen_lean_years" (one-launch years run on a lean cache; also counted in "frozen_persistent_years"),
    "frozen_lds_bits" (the bits of option "frozen_coef_lds" in effect in the one-launch year launched last, after fitting),
+   "frozen_early_bits" (option "frozen_early" as in effect in that year: 0 wherever "frozen_lds_bits" lacks 16 and 32),
+   "frozen_step_sums_hash" (64-bit FNV-1a hash of the bits of the step sums the last whole-year check of a frozen year read: the
+   norm sums of every step's last Newton iteration and of the one before -- the same for the same year by whatever path),
    "frozen_forced_years" (one-launch years only option "frozen_forced" made possible; also counted in "frozen_persistent_years",
    and in "frozen_lean_years" where lean),
    "frozen_phosphorus_years" (one-launch years of the phosphorus module, option "frozen_phosphorus"; also counted in
@@ -464,7 +467,12 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    own three stage values in registers from one Newton phase to the next; bits 4 and 8 need "frozen_by_column"; bits 16 and 32
    exist on top of the other four, on the full cache, at five to seven levels per lane -- a cache in pieces has 32 only together
    with 16 --; what does not fit the compute unit's LDS is given up, 16 first: counter "frozen_lds_bits" is the set the year
-   launched last ran with), "frozen_by_column" (1,
+   launched last ran with), "frozen_early" (1, default, or 0: a wave that carries the whole own state -- "frozen_lds_bits" 63 --
+   forms the norm partial of an update part behind that part's stores, while they are on their way, and stores it behind its
+   hand-over flag instead of in front of the stores its neighbours wait for; the same operations; counter "frozen_early_bits"),
+   "frozen_sums_poison" (0, default, or 1; for tests: the rows of norm partials are filled with NaN before every frozen year, so
+   that a partial the year does not store fails its check instead of passing on what an earlier year left there),
+   "frozen_by_column" (1,
    default: from five levels per lane a workgroup is ONE ypos column with all its tracers, so that what is the same for every
    tracer of a column is shared through LDS; 2: from three levels per lane; 0: adjacent columns of one tracer),
    "hook_spec_depth" (1 or 2, default 2: whole Newton iterations a controller with a vector norm hook queues ahead of a verdict), "barrier_timeout_ms" (longest wait at a grid barrier of the one-launch years, default 2000:

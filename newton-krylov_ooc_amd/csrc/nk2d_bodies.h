@@ -892,6 +892,7 @@ __device__ __forceinline__ void w_lds_put(double* s, int r, int lane, const doub
 // and, no LDS at all,
 //   bit 5  z   : the column's own three stage values stay in the wave's registers from the update part of one phase to the
 //                stage part of the next (OwnState::z)
+//   bit 7  norm : the update part may form the norm partial behind its stores and leave it to the caller to store (LateNorm)
 struct LdsSrc {
     const double* coef;
     double* w;
@@ -913,10 +914,35 @@ __device__ __forceinline__ void col_lds_get(const double* s, int r, int lane, do
 #pragma unroll
     for (int e = 0; e < E; ++e) v[e] = s[(r * E + e) * 64 + lane];
 }
+// The norm partial of an update part out of the way of the hand-over (CL bit 7; option "frozen_early" of the one-launch year).
+// Nothing on the device reads the partial, yet its divisions and the sum over the wave stood in front of the stores the
+// neighbours wait for, and its own store among those the hand-over drains.  With `defer` set the update part issues its stores
+// of Z (or of y_new and the next Z) first and forms the partial behind them -- the same operations on the same values, while
+// the stores are on their way --, and leaves the sum here: the caller stores it behind NeighbourSync::publish()
+// (`pending`, wave-uniform, says there is one), where the next publish() or the end of the kernel drains it.
+struct LateNorm {
+    double acc;
+    double* part;
+    int defer, pending;
+};
+// sum over the wave of the squared scaled increments (radau.py:113-129): the expressions of the update part of newton_fused_body
+template <int E>
+__device__ __forceinline__ double norm_partial_sum(const DevP& P, const double (&yy)[E], const double (&d0v)[E],
+                                                   const double (&d1v)[E], const double (&d2v)[E]) {
+    double acc = 0.0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const double sc = P.atol + fabs(yy[e]) * P.rtol;
+        const double d0 = d0v[e] / sc, d1 = d1v[e] / sc, d2 = d2v[e] / sc;
+        acc += (d0 * d0 + d1 * d1) + d2 * d2;
+    }
+    return wave_sum(acc);
+}
+
 template <int E, int KIND, int FACTOR, int STAGE, int MP = 0, int FINAL = 0, int CL = 0>
 __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs& A, int task, int lane,
                                                   const FinalArgs* fin = nullptr, const LdsSrc* lds = nullptr,
-                                                  OwnState<E>* own = nullptr) {
+                                                  OwnState<E>* own = nullptr, LateNorm* late = nullptr) {
     const double* coef_lds = (CL & 1) ? lds->coef : nullptr;
     double* w_lds = (CL & 2) ? lds->w : nullptr;
     (void)coef_lds; (void)w_lds;
@@ -1164,7 +1190,9 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         load_col<E>(A.st.w + A.st.nv, task, lane, w1);
         load_col<E>(A.st.w + 2 * A.st.nv, task, lane, w2);
     }
-    if (norm) {
+    bool norm_late = false;     // (the partial behind the stores below, its store left to the caller: LateNorm)
+    if constexpr (CL & 128) norm_late = norm && late->defer != 0;
+    if (norm && !norm_late) {
         double acc = 0.0;
 #pragma unroll
         for (int e = 0; e < E; ++e) {
@@ -1227,6 +1255,9 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
             }
         }
         if constexpr ((CL & 48) != 0) own->valid = 1;
+        if constexpr (CL & 128) {
+            if (norm_late) { late->acc = norm_partial_sum<E>(P, yy, fr, fcr, fci); late->part = A.part + task; late->pending = 1; }
+        }
         return;
     }
     double* zout = A.st.zout;
@@ -1249,6 +1280,9 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         }
     }
     if constexpr ((CL & 48) != 0) own->valid = 1;
+    if constexpr (CL & 128) {
+        if (norm_late) { late->acc = norm_partial_sum<E>(P, yy, fr, fcr, fci); late->part = A.part + task; late->pending = 1; }
+    }
 }
 
 
@@ -2018,6 +2052,68 @@ struct NeighbourSync {
     int* lds_ok;
     long long spin_ticks;
     int fences;
+#ifdef NK2D_FROZEN_CLOCKS
+    // probe build only: ticks of s_memrealtime (100 MHz) wave 0 of a workgroup spent (a) draining its stores in publish(),
+    // (b) between its flag store and the poll's match -- whatever the caller does in between included
+    long long ck_drain = 0, ck_wait = 0, ck_flag = 0;
+#endif
+    // The hand-over in two halves, for a caller that has work of its own column to do while the neighbours catch up.
+    // publish(): every wave's write-through stores drained, the workgroup joined, the flag stored.  wait(): the bounded poll
+    // of the two neighbours' flags, the workgroup joined again.  Between the two a wave may compute on what its compute unit
+    // holds; every load of a neighbour's bytes stays behind wait(), every store another workgroup reads in front of publish()
+    // (a store issued in between is drained by the next publish() or the end of the kernel, and may be read by no other
+    // workgroup sooner)
+    __device__ __forceinline__ void publish() {
+#ifdef NK2D_FROZEN_CLOCKS
+        const long long ck0 = (long long)__builtin_amdgcn_s_memrealtime();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ck_drain += (long long)__builtin_amdgcn_s_memrealtime() - ck0;
+#else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+        if (fences) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __syncthreads();
+        ++phase;
+        if (threadIdx.x == 0) __hip_atomic_store(flags + (size_t)me * 32, phase, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef NK2D_FROZEN_CLOCKS
+        ck_flag = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
+    }
+    // (the poll below is also the second half of sync(): a change to the time limit or the abort handling goes into both)
+    __device__ __forceinline__ bool wait() {
+        if (threadIdx.x < 64) {
+            const int lane = threadIdx.x;
+            const int other = (lane == 0) ? left : ((lane == 1) ? right : -1);
+            int good = 1;
+            long long spins = 0;
+            const long long t_begin = (long long)__builtin_amdgcn_s_memrealtime();
+            for (;;) {
+                unsigned v = phase;
+                if (other >= 0) v = __hip_atomic_load(flags + (size_t)other * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (__all((int)(v >= phase))) break;
+                const int ab = __builtin_amdgcn_readfirstlane(
+                    (lane == 0) ? __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0);
+                const bool late = ((++spins & 63) == 0 || spin_ticks == 0) &&
+                                  (long long)__builtin_amdgcn_s_memrealtime() - t_begin > spin_ticks;
+                if (late || spins > 4000LL * NK2D_SPIN_LIMIT || ab != 0) {
+                    if (lane == 0) __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    good = 0;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(1);
+            }
+            if (lane == 0) *lds_ok = good;
+#ifdef NK2D_FROZEN_CLOCKS
+            ck_wait += (long long)__builtin_amdgcn_s_memrealtime() - ck_flag;
+#endif
+        }
+        __syncthreads();
+        if (fences) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        return *lds_ok != 0;
+    }
+    // publish(); wait(); for every caller that has nothing to do in between -- as one text, the one it always was: composed of
+    // the two halves, the kernels that call it came out of the compiler with other register counts
+    // (profiles/r11_frozen_early_kernel_resources.log).  The same statements as publish() and wait(): a change goes into both
     __device__ __forceinline__ bool sync() {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (fences) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -2304,7 +2400,11 @@ struct FrozenArgs {
     long long spin_ticks;
     int fences;
     int coef_lds;                // option "frozen_coef_lds" (bits of LdsSrc) as frozen_lds_shape() fitted it: what a wave finds in LDS (bits 2, 3, 4
-                                 // need `by_column`) and, bit 5, keeps in registers
+                                 // need `by_column`) and, bit 5, keeps in registers.  Bit 8: option "frozen_early", set only on top of all
+                                 // six (NK2D_FROZEN_EARLY_OF; a field of its own moved the register counts of kernels that never read it).
+                                 // Every other reader -- the kernel's `& bit` and non-zero tests, frozen_factor_phase(), frozen_lds_doubles()
+                                 // -- looks at single bits below 64 or at "any bit set", and bit 8 is never set alone: it changes none of them
+#define NK2D_FROZEN_EARLY_OF(coef_lds) (((coef_lds) >> 8) & 1)
     int by_column;               // 1: a workgroup is ONE ypos column with all its tracers (a wave each) instead of adjacent columns of one tracer
     // option "frozen_forced" bit 2 (forced module with a thresholded sink, lean cache): the rows' file-source planes at their Jacobian
     // times, [n][np] behind J in the slab (a cache in pieces: PieceTab::oS), and 1 where the year forms UPR from them

@@ -32,6 +32,8 @@
 #define NK2D_CKPT_EVERY 128      /* steps between two checkpoints of a frozen year */
 
 
+// option "frozen_early" as a context starts with it (1: the norm partial of an update part behind its stores and the hand-over's flag)
+#define NK2D_FROZEN_EARLY_DEFAULT 1
 struct nk2d_ctx {
     nk2d_desc d;
     int nz, ny, tc, E, nzp, ncol, nreg;
@@ -141,6 +143,8 @@ struct nk2d_ctx {
     int frozen_wpb;       // option "frozen_wpb": columns (waves) per workgroup of the wave-per-column one-launch year with neighbour hand-over
     int frozen_coef_lds;  // option "frozen_coef_lds": the one-launch year keeps the static coefficients of a wave's column in LDS
     int frozen_lds_bits;  // counter "frozen_lds_bits": the bits of it in effect in the one-launch year launched last, after fitting
+    int frozen_early;     // option "frozen_early": a wave of the one-launch year forms its norm partials out of the way of the hand-over
+    int frozen_early_bits; // counter "frozen_early_bits": the option in effect in the one-launch year launched last
     int frozen_by_column; // option "frozen_by_column": a workgroup of the one-launch year is one ypos column with all its tracers
     int frozen_alloc_async;   // option "frozen_alloc_async": a schedule cache above 8 GB is allocated by a thread of its own
     int frozen_cache_after;   // option "frozen_cache_after": frozen years of a schedule that run launch by launch before its cache is built (default 0; -1: 0 for a cache below 8 GB, 3 above)
@@ -270,6 +274,12 @@ struct nk2d_ctx {
     int win_open, win_launches;
     int64_t win_seq;
     double win_bytes;
+    // the check behind a frozen year, made observable (tests): option "frozen_sums_poison" fills the rows of STEP_PART with NaN
+    // before every frozen year -- a partial that is not stored, or stored elsewhere, then fails the year's check instead of
+    // passing on what the year before left there --; counter "frozen_step_sums_hash" is a 64-bit FNV-1a hash of the bits of
+    // the step sums the last whole-year check read (last iteration of every step, and the one before where there is one)
+    int frozen_sums_poison = 0;
+    int64_t frozen_step_sums_hash = 0;
 };
 
 #define NK2D_CHECK(ctx, call)                                                        \

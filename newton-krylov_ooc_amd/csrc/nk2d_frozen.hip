@@ -2,6 +2,9 @@
 #include "nk2d_bodies.h"
 
 #include <algorithm>
+#ifdef NK2D_FROZEN_CLOCKS
+#include <cstdio>
+#endif
 #include <vector>
 
 // the tables of row i of a cache in pieces: in the piece that holds the row
@@ -966,6 +969,10 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
     if (want_src || want_phos) P.UPR = fc->upr;
     NK2D_TRY(frozen_lds_shape(c, want_phos, want_lean, want_pieces, &A.coef_lds, &A.by_column));
     c->frozen_lds_bits = A.coef_lds;
+    c->frozen_early_bits = (A.coef_lds & 48) == 48 ? c->frozen_early : 0;   // (48 is there only where the own state is compiled in: frozen_lds_shape)
+    // (invariant: bit 8 only together with bits 0 - 5.  Everything that takes A.coef_lds from here on -- frozen_lds_doubles() in the
+    // launch functions, the kernel -- tests bits below 64 or non-zero, which bit 8 on top of 63 does not change)
+    A.coef_lds |= c->frozen_early_bits << 8;
     // option "frozen_team": a workgroup per column (four waves: newton_team_body) instead of a wave per column, up to two levels per
     // lane.  Measured in round 3 (profiles/r03_frozen_team.log, r03_frozen_nbsync.log): teams want a CU each and beat the
     // wave-per-column year at every such size -- 26^2 9.4 ms, 52^2 14.9, 104^2 27.0 with the neighbour hand-over.
@@ -1008,6 +1015,10 @@ int nk2d_frozen_persistent(nk2d_ctx* c, const double* sched, int64_t n, std::vec
         NK2D_CHECK(c, hipMemcpyAsync(c->hYR_OUT, c->YR_OUT, sizeof(double) * 32, hipMemcpyDeviceToHost, nk2d_s(c)));
         NK2D_CHECK(c, hipStreamSynchronize(nk2d_s(c)));
         if ((int)o[0] != 0 || (int64_t)o[1] != n) return 2;
+#ifdef NK2D_FROZEN_CLOCKS
+        std::fprintf(stderr, "frozen clocks (early %d): %.0f phases, per phase drain %.3f us, flag store to poll match %.3f us, rest %.3f us; kernel %.3f ms\n",
+                     c->frozen_early_bits, o[11], 0.01 * o[8] / o[11], 0.01 * o[9] / o[11], 0.01 * (o[10] - o[8] - o[9]) / o[11], 1.0e-5 * o[10]);
+#endif
     }
     if (team) c->frozen_team_years++;
     {   // the launch itself, between two events on the context's stream (bench.py's roofline of the one-launch year)

@@ -31,6 +31,9 @@
         nb_right = (cl % P.ny < P.ny - 1) ? wg + 1 : -1;
     }
     NeighbourSync nbs{(unsigned*)((char*)A.arrive + 8192), A.abort_flag, wg, nb_left, nb_right, 0u, &lds_ok, A.spin_ticks, A.fences};
+#ifdef NK2D_FROZEN_CLOCKS
+    const long long ck_begin = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
     const size_t nv = A.C.nv;
     int swapY = 0, swapZ = 0, status = 0, done = 0;
     int pc_p = 0, pc_r = 0;     // PIECES: row i is row pc_r of piece pc_p (i = pc_p rows + pc_r, kept by counting: no division)
@@ -102,6 +105,10 @@
     }
     int lds_step = -1;      // the step whose constants the step block / the pivots hold
     (void)lds_step;
+    // option "frozen_early" (bit 8 of A.coef_lds, set by the host only where the year carries the whole own state, CL 63): the wave
+    // forms the norm partial of an update part behind that part's stores and stores it behind the hand-over's flag (LateNorm)
+    LateNorm late = {0.0, nullptr, (OWN && by_col && own_bits == 48) ? uni_i(NK2D_FROZEN_EARLY_OF(A.coef_lds)) : 0, 0};
+    (void)late;
     // first attempt of the year: Z0 = 0, W0 = 0 (radau.py:445-446)
     if (col_wave && (!TEAM || tw == 0)) {
         double zero[E];
@@ -262,7 +269,7 @@
                             if (m == 1) { newton_single_body<E, MPX, 1>(P, FA, wave, lane, &Fin); taken = true; }
                         }
                         if constexpr (OWN) {
-                            if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 63>(P, FA, wave, lane, &Fin, &L, &own); taken = true; }
+                            if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 191>(P, FA, wave, lane, &Fin, &L, &own, &late); taken = true; }
                             else if (!PIECES && own_bits == 32) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 47>(P, FA, wave, lane, &Fin, &L, &own); taken = true; }
                             else if (own_bits == 16) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 31>(P, FA, wave, lane, &Fin, &L, &own); FZ_OWN_DEAD() taken = true; }
                         }
@@ -294,7 +301,7 @@
                             if (m == 1) { newton_single_body<E, MPX, 0>(P, FA, wave, lane); taken = true; }
                         }
                         if constexpr (OWN) {
-                            if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 63>(P, FA, wave, lane, nullptr, &L, &own); taken = true; }
+                            if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 191>(P, FA, wave, lane, nullptr, &L, &own, &late); taken = true; }
                             else if (!PIECES && own_bits == 32) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 47>(P, FA, wave, lane, nullptr, &L, &own); taken = true; }
                             else if (own_bits == 16) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 31>(P, FA, wave, lane, nullptr, &L, &own); FZ_OWN_DEAD() taken = true; }
                         }
@@ -310,7 +317,17 @@
                     if (do_stage && do_update) swapZ ^= 1;
                 }
                 src = 1 - src;
-                FZ_SYNC()
+                if constexpr (OWN) {
+                    // the hand-over in two halves: the flag first, then the store nobody waits for, then the poll
+                    nbs.publish();
+                    if (late.pending) {
+                        if (lane == 0) st_mp<MPX>(late.part, late.acc);
+                        late.pending = 0;
+                    }
+                    if (!nbs.wait()) { status = 1; goto finish; }
+                } else {
+                    FZ_SYNC()
+                }
             }
         }
         if (with_err) {
@@ -366,6 +383,14 @@ finish:
     // no barrier behind the last phase: every workgroup reports a failure of its own (the host cleared `out`), the first the
     // rest -- a workgroup that gave up raised the abort flag, its neighbours give up on it in turn
     if (status != 0 && threadIdx.x == 0) A.out[0] = (double)status;
+#ifdef NK2D_FROZEN_CLOCKS
+    // probe build: wave 0 of the middle workgroup reports its three spans in spare slots of `out` (ticks of 10 ns: the store
+    // drains, flag store to poll match, the whole kernel -- the rest of the phases is the difference) and its phase count
+    if (wg == (int)(gridDim.x / 2) && threadIdx.x == 0) {
+        A.out[8] = (double)nbs.ck_drain; A.out[9] = (double)nbs.ck_wait;
+        A.out[10] = (double)((long long)__builtin_amdgcn_s_memrealtime() - ck_begin); A.out[11] = (double)nbs.phase;
+    }
+#endif
     if (wg == 0 && threadIdx.x == 0) {
         A.out[1] = (double)done; A.out[2] = (double)swapY; A.out[3] = (double)swapZ; A.out[4] = (double)nbs.phase;
     }

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
@@ -1087,6 +1088,9 @@ int run_replay(Ctl& s, const double* sched, int64_t n, bool check) {
         NK2D_CHECK(c, hipMalloc((void**)&c->STEP_PART, sizeof(double) * (size_t)(3 * n) * c->ncol));
         c->step_part_rows = (size_t)(3 * n);
     }
+    // (option "frozen_sums_poison": whatever an earlier year left in the rows is no longer a sum that passes the check)
+    if (c->frozen_sums_poison)
+        NK2D_CHECK(c, hipMemsetAsync(c->STEP_PART, 0xFF, sizeof(double) * (size_t)(3 * n) * c->ncol, nk2d_s(c)));
     std::vector<double> mine;            // the schedule with the iteration counts a resume has raised
     const double* cur = sched;
     std::vector<double> sums((size_t)3 * n);
@@ -1097,6 +1101,22 @@ int run_replay(Ctl& s, const double* sched, int64_t n, bool check) {
     const double n_unknowns = hooked ? (double)c->tc * c->nz * c->ny : s.n_total;
     // SciPy's convergence test on the last recorded iteration of the rows from `from` on: the first row that fails, or -1
     auto first_unconverged = [&](const double* rows, int64_t from) -> int64_t {
+        if (from == 0) {
+            // counter "frozen_step_sums_hash": the bits of every sum this check reads (FNV-1a, 64 bits)
+            uint64_t h = 1469598103934665603ull;
+            auto mix = [&](double v) {
+                unsigned char b[sizeof(double)];
+                std::memcpy(b, &v, sizeof(double));
+                for (unsigned char x : b) { h ^= x; h *= 1099511628211ull; }
+            };
+            for (int64_t i = 0; i < n; ++i) {
+                const int n_it = (int)rows[i * NK2D_SCHED_WIDTH + 3];
+                if (n_it < 1) continue;
+                mix(sums[3 * i]);
+                if (n_it >= 2) mix(sums[3 * i + 1]);
+            }
+            c->frozen_step_sums_hash = (int64_t)h;
+        }
         for (int64_t i = from; i < n; ++i) {
             const int n_it = (int)rows[i * NK2D_SCHED_WIDTH + 3];
             if (n_it < 1) continue;

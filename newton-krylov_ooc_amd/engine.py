@@ -231,6 +231,9 @@ class ModuleEngine:
         # 2 the 256-register flavour where that one is not resident, 3 that flavour wherever it exists (csrc/nk2d_frozen.hip)
         if "NK2D_FROZEN_PHOSPHORUS" in os.environ:
             self.set_option("frozen_phosphorus", float(os.environ["NK2D_FROZEN_PHOSPHORUS"]))
+        # the one-launch frozen year's norm partials out of the way of the hand-over between workgroups (csrc/nk2d_frozen_body.inc)
+        if "NK2D_FROZEN_EARLY" in os.environ:
+            self.set_option("frozen_early", float(os.environ["NK2D_FROZEN_EARLY"]))
         # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_TWO_ENDED" in os.environ:
             self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
