@@ -180,6 +180,42 @@ def test_growth_and_reuse():
     eng.close()
 
 
+def test_walk_through_every_form():
+    """ONE store through every form in turn -- slab, pieces, slab again, lean slab, lean pieces, full slab: after every change the
+    launch-per-phase year's bits, one more one-launch year, exactly one more build, the other form gone (pieces held, lean
+    flag, bytes = 8 x rows held x doubles of a row of that form); a repeat year in the same form builds and allocates nothing"""
+    eng = _iage(26)
+    eng.set_option("frozen_err_check", 7)
+    _, x, xp = _state(eng)
+    _, _, sched = eng.comp_fcn(x, record=True)
+    n, B = len(sched), 7
+    tc = eng.shape[0]                                            # one level per lane: kv_len = np = 26 x 64, nv = tc np, ntab = tc 26 x 14 x 64
+    plane, nv, ntab = 26 * 64, tc * 26 * 64, tc * 26 * 14 * 64
+    row_bytes = {0: 8 * (3 * plane + 5 * plane + 3 * nv + 3 * ntab), 1: 8 * (3 * plane + 5 * plane)}
+    eng.set_option("frozen_persistent", 0)
+    lpp = eng.download(eng.comp_fcn_frozen(xp, sched)[0])
+    eng.set_option("frozen_persistent", 1)
+    eng.set_option("frozen_cache_piece_rows", B)
+    for pieces, lean in ((0, 0), (1, 0), (0, 0), (0, 1), (1, 1), (0, 0)):
+        eng.set_option("frozen_cache_pieces", pieces)
+        eng.set_option("frozen_cache_lean", lean)
+        years, builds = eng.counter("frozen_persistent_years"), eng.counter("frozen_cache_builds")
+        got = eng.download(eng.comp_fcn_frozen(xp, sched)[0])
+        assert np.array_equal(got, lpp), (pieces, lean)
+        assert eng.counter("frozen_persistent_years") == years + 1 and eng.counter("frozen_cache_builds") == builds + 1, (pieces, lean)
+        assert eng.counter("frozen_cache_pieces") == (math.ceil(n / B) if pieces else 0), (pieces, lean)
+        assert eng.counter("frozen_cache_lean") == lean, (pieces, lean)
+        rows_held = math.ceil(n / B) * B if pieces else n + n // 6 + 16
+        assert eng.counter("frozen_cache_bytes") == rows_held * row_bytes[lean], (pieces, lean)
+        allocs = eng.counter("frozen_cache_piece_allocs")
+        again = eng.download(eng.comp_fcn_frozen(xp, sched)[0])
+        assert np.array_equal(again, lpp), (pieces, lean)
+        assert eng.counter("frozen_persistent_years") == years + 2 and eng.counter("frozen_cache_builds") == builds + 1, (pieces, lean)
+        assert eng.counter("frozen_cache_piece_allocs") == allocs, (pieces, lean)
+        assert eng.counter("frozen_cache_bytes") == rows_held * row_bytes[lean], (pieces, lean)
+    eng.close()
+
+
 def test_routing():
     from nk_ooc_amd.engine import phosphorus_engine
     from nk_ooc_amd.grid import Grid2d

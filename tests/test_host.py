@@ -280,6 +280,21 @@ def test_host_arithmetic_under_address_sanitizer():
     assert "hostmath ok" in res.stdout
 
 
+def test_frozen_plan_under_address_sanitizer():
+    """csrc/nk2d_frozen_plan.h (the schedule cache of the one-launch frozen year: eligibility, form, admission, growth, the
+    layout of a block, what lives in LDS) against known answers, built with a plain g++ under -fsanitize=address,undefined
+    and run on the CPU: `make asan-host`, tests/host_asan/test_frozen_plan.cpp"""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None or shutil.which("make") is None:
+        pytest.skip("no host compiler")
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "newton-krylov_ooc_amd", "csrc")
+    res = subprocess.run(["make", "-C", csrc, "asan-host"], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    assert "frozen plan ok" in res.stdout
+
+
 def test_solver_state_file_is_what_json_dump_writes(tmp_path):
     """the state file is put together from cached per-value text (an indented dump runs in json's pure-Python encoder, six
     times per Krylov iteration): byte for byte what json.dump(data, indent=2) writes, after every kind of change"""
