@@ -270,7 +270,8 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    "spec_front_launches_dropped", "err_estimates_queued", "err_estimates_dropped" (work queued ahead of a verdict); of the
    preconditioner (option "pc_two_ended"): "pc_setup_rounds" (dependent inversion rounds of the last block elimination: ny,
    or ny / 2 + 1 from both ends), "pc_sub_launches" (dependent mat-vec launches of the last block substitution: 2 ny - 1,
-   or at most ny + 2). */
+   or at most ny + 2); (option "pc_pivot_wave") "pc_pivot_wave_steps" (panel steps of the last block elimination that ran
+   a one-wave pivot inversion: 0, or ceil(m / 32) * "pc_setup_rounds"). */
 int nk2d_get_counter(nk2d_ctx* ctx, const char* name, int64_t* out);
 /* hash of everything a recorded schedule depends on besides the state: grid, module description, tolerances, the
    controller options (jac_fresh, jac_stage, lin_tol, min_sweeps, growth_cap, factor storage), the library version and a
@@ -483,7 +484,11 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    once -- two chains of half the length in the same launches, a twisted factorisation -- and meets in column ny / 2, and
    the substitution advances both chains per launch.  Read by nk2d_precond_setup, nk2d_precond_setup_states and
    nk2d_shift_factor; nk2d_precond_apply and nk2d_shift_solve follow the value of the set-up they use.  Composes with
-   "pc_fp32" and "pc_fused"; with "pc_valu" 1 the set-up is refused.  Counters "pc_setup_rounds", "pc_sub_launches") */
+   "pc_fp32" and "pc_fused"; with "pc_valu" 1 the set-up is refused.  Counters "pc_setup_rounds", "pc_sub_launches"),
+   "pc_pivot_wave" (0, default, or 1; opt-in: the 32 x 32 pivot blocks of the preconditioner's Gauss-Jordan inversions are
+   inverted by ONE wave in registers -- no LDS round trip and no barrier per pivot -- instead of by four waves through LDS:
+   the same operations in the same order, the same bits.  Read at every set-up as "pc_two_ended" is; composes with
+   "pc_fused", "pc_valu", "pc_two_ended" and "pc_fp32".  Counter "pc_pivot_wave_steps") */
 int nk2d_set_option(nk2d_ctx* ctx, const char* name, double value);
 
 /* block until every operation queued on the context's stream has finished */

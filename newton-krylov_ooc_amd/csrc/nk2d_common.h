@@ -219,6 +219,8 @@ struct nk2d_ctx {
     int pc_refine; // ... with this many refinement steps per apply against the exact operator (option "pc_refine", default 1)
     int pc_two_ended;   // option "pc_two_ended": 0 (default) the block elimination runs over ypos = 0 .. ny - 1, 1 from both ends at once (read at set-up; a factorisation keeps the value it was made with)
     int64_t pc_setup_rounds, pc_sub_launches;   // counters (nk2d_get_counter): dependent inversion rounds of the last elimination, dependent mat-vec launches of the last substitution
+    int pc_pivot_wave;  // option "pc_pivot_wave": 0 (default) the 32 x 32 pivot blocks of the Gauss-Jordan inversions are inverted by four waves through LDS, 1 by one wave in registers -- the same bits (read at every set-up)
+    int64_t pc_pivot_wave_steps;   // counter: panel steps of the last elimination that ran a wave flavour
 
     // optional dense-output sampling of the running comp_fcn (history files)
     int hist_n, hist_next;

@@ -213,12 +213,82 @@ __global__ void k_pc_schur_ends(PcDev P, int nsys, PcSchurEnd e0, PcSchurEnd e1,
 // ---------------------------------------------------------------------------------
 #define PC_NB 32
 
+// The pivot block inverted by ONE wave in registers (option "pc_pivot_wave"): the 32 dependent eliminations of the LDS
+// ping-pong below (k_pc_gj_rows, pc_invert_block) without LDS and without a barrier, operation for operation --
+//   piv = 1.0 / a[pp][pp];  prow = ((cc == pp) ? 1.0 : a[pp][cc]) * piv;
+//   a[r][cc] = (r == pp) ? prow : fma(-a[r][pp], prow, (cc == pp) ? 0.0 : a[r][cc])
+// on the block as it stood at the start of pivot pp: the same bits.  Lane (h, cc) = (lane >> 5, lane & 31) holds
+// a[q] = A[16 h + q][cc], q = 0 .. 15.  The pivot loop is unrolled (static register indices) and keeps the wave-uniform
+// guard pp < nb.  Per pivot: the row A[pp][.] reaches the other half of the wave by one half-swap (v_permlane32_swap, a
+// pair for the two dwords), the diagonal entry by v_readlane, the 16 column factors A[16 h + q][pp] by a broadcast from
+// lane pp of each half, __shfl(x, pp, 32) (ds_bpermute: the LDS crossbar, no LDS memory).  (The transposed layout, a lane
+// per row, exchanges the two broadcasts and multiplies 16 entries of the pivot row per lane by piv instead of one; the
+// column factors by v_readlane of both halves as scalar operands compile to 266 instead of 150 instructions per pivot:
+// DESIGN.md section 4.)
+typedef unsigned pc_v2u __attribute__((ext_vector_type(2)));
+
+// x of lane `from` (wave-uniform), in every lane
+__device__ __forceinline__ double pc_wave_lane(double x, int from) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), from);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), from);
+    return __hiloint2double(hi, lo);
+}
+
+// x of the lanes of half `hp`, in both halves of the wave: v_permlane32_swap vdst, src exchanges lanes 32 .. 63 of vdst
+// with lanes 0 .. 31 of src, so with both operands x the first result is the lower half's x twice, the second the upper's
+__device__ __forceinline__ double pc_wave_half(double x, int hp) {
+    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+    const pc_v2u rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const pc_v2u rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return hp ? __hiloint2double((int)rh[1], (int)rl[1]) : __hiloint2double((int)rh[0], (int)rl[0]);
+}
+
+__device__ __forceinline__ void pc_invert_block_wave(double (&a)[PC_NB / 2], int lane, int nb) {
+    const int h = lane >> 5, cc = lane & 31;
+#pragma unroll
+    for (int pp = 0; pp < PC_NB; ++pp) {
+        if (pp < nb) {
+            const int hp = pp >> 4, qp = pp & 15;
+            const double rowv = pc_wave_half(a[qp], hp);            // A[pp][cc]
+            const double piv = 1.0 / pc_wave_lane(rowv, pp);        // 1 / A[pp][pp]
+            const double prow = ((cc == pp) ? 1.0 : rowv) * piv;
+            // the column factors A[16 h + q][pp], taken before anything of this pivot is written; then "(cc == pp) ? 0.0 : old" as
+            // a move under the lane mask of column pp (its entries ARE the column factors, held in f by now)
+            double f[PC_NB / 2];
+#pragma unroll
+            for (int q = 0; q < PC_NB / 2; ++q) f[q] = __shfl(a[q], pp, 32);
+            if (cc == pp) {
+#pragma unroll
+                for (int q = 0; q < PC_NB / 2; ++q) a[q] = 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < PC_NB / 2; ++q) {
+                const double upd = __builtin_fma(-f[q], prow, a[q]);
+                a[q] = (q == qp && h == hp) ? prow : upd;
+            }
+        }
+    }
+}
+
+// the wave's entries of the pivot block at rows / columns p0 .. p0 + nb of `src`, padded with the identity
+__device__ __forceinline__ void pc_wave_load_block(double (&a)[PC_NB / 2], int lane, int m, int p0, int nb,
+                                                   const double* __restrict__ src, size_t base) {
+    const int h = lane >> 5, cc = lane & 31;
+#pragma unroll
+    for (int q = 0; q < PC_NB / 2; ++q) {
+        const int r = 16 * h + q;
+        a[q] = (r < nb && cc < nb) ? src[base + (size_t)(p0 + r) * m + (p0 + cc)] : ((r == cc) ? 1.0 : 0.0);
+    }
+}
+
 // R[p][c] for p < nb, c < m.  Every workgroup first inverts the nb x nb pivot block itself (in LDS, the
 // Gauss-Jordan without pivoting): redundant arithmetic on 1024 numbers instead of a launch of a
-// single workgroup that everything else would wait for.
+// single workgroup that everything else would wait for.  PW = 1 (option "pc_pivot_wave"): wave 0 inverts it in registers
+// and leaves the inverse in ab[0]; one barrier instead of one per pivot.
+template <int PW>
 __global__ void __launch_bounds__(256) k_pc_gj_rows(int m, int p0, int nb, const double* __restrict__ src,
                                                     double* __restrict__ rows) {
-    __shared__ double ab[2][PC_NB][PC_NB + 1];   // ping-pong: one barrier per pivot
+    __shared__ double ab[PW ? 1 : 2][PC_NB][PC_NB + 1];   // ping-pong: one barrier per pivot
     const int tr = blockIdx.z;
     const size_t base = (size_t)tr * m * m;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -227,32 +297,44 @@ __global__ void __launch_bounds__(256) k_pc_gj_rows(int m, int p0, int nb, const
     double col[PC_NB];
 #pragma unroll
     for (int q = 0; q < PC_NB; ++q) col[q] = (c < m && q < nb) ? src[base + (size_t)(p0 + q) * m + c] : 0.0;
-    // the thread's four entries of the pivot block: column cc, rows r0 + 8 q
-    const int r0 = threadIdx.x / PC_NB, cc = threadIdx.x - r0 * PC_NB;
-    double mine[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r = r0 + 8 * q;
-        mine[q] = (r < nb && cc < nb) ? src[base + (size_t)(p0 + r) * m + (p0 + cc)] : ((r == cc) ? 1.0 : 0.0);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ab[0][r0 + 8 * q][cc] = mine[q];
-    __syncthreads();
     int cur = 0;
-    for (int pp = 0; pp < nb; ++pp) {
-        double (*a)[PC_NB + 1] = ab[cur];
-        const double piv = 1.0 / a[pp][pp];
-        const double prow = ((cc == pp) ? 1.0 : a[pp][cc]) * piv;
+    if constexpr (PW) {
+        if (threadIdx.x < 64) {
+            const int lane = threadIdx.x;
+            double blk[PC_NB / 2];
+            pc_wave_load_block(blk, lane, m, p0, nb, src, base);
+            pc_invert_block_wave(blk, lane, nb);
+#pragma unroll
+            for (int q = 0; q < PC_NB / 2; ++q) ab[0][16 * (lane >> 5) + q][lane & 31] = blk[q];
+        }
+        __syncthreads();
+    } else {
+        // the thread's four entries of the pivot block: column cc, rows r0 + 8 q
+        const int r0 = threadIdx.x / PC_NB, cc = threadIdx.x - r0 * PC_NB;
+        double mine[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int r = r0 + 8 * q;
-            const double f = a[r][pp];
-            const double old = (cc == pp) ? 0.0 : mine[q];
-            mine[q] = (r == pp) ? prow : __builtin_fma(-f, prow, old);
-            ab[1 - cur][r][cc] = mine[q];
+            mine[q] = (r < nb && cc < nb) ? src[base + (size_t)(p0 + r) * m + (p0 + cc)] : ((r == cc) ? 1.0 : 0.0);
         }
-        cur = 1 - cur;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ab[0][r0 + 8 * q][cc] = mine[q];
         __syncthreads();
+        for (int pp = 0; pp < nb; ++pp) {
+            double (*a)[PC_NB + 1] = ab[cur];
+            const double piv = 1.0 / a[pp][pp];
+            const double prow = ((cc == pp) ? 1.0 : a[pp][cc]) * piv;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = r0 + 8 * q;
+                const double f = a[r][pp];
+                const double old = (cc == pp) ? 0.0 : mine[q];
+                mine[q] = (r == pp) ? prow : __builtin_fma(-f, prow, old);
+                ab[1 - cur][r][cc] = mine[q];
+            }
+            cur = 1 - cur;
+            __syncthreads();
+        }
     }
     double (*a)[PC_NB + 1] = ab[cur];
     if (c >= m) return;
@@ -463,25 +545,36 @@ __device__ __forceinline__ int pc_invert_block(double (*ab)[PC_NB][PC_NB + 1], d
 }
 
 // inverse of the FIRST pivot block of every system (the later ones come out of k_pc_gj_step): pinv [nsys][32][32], identity
-// beyond nb
-__global__ void __launch_bounds__(256) k_pc_pivot_invert(int m, int p0, int nb, const double* __restrict__ src, double* __restrict__ pinv) {
-    __shared__ double ab[2][PC_NB][PC_NB + 1];
+// beyond nb.  PW = 1 (option "pc_pivot_wave"): ONE wave per system, in registers
+template <int PW>
+__global__ void __launch_bounds__(PW ? 64 : 256) k_pc_pivot_invert(int m, int p0, int nb, const double* __restrict__ src, double* __restrict__ pinv) {
     const int tr = blockIdx.z;
     const size_t base = (size_t)tr * m * m;
-    const int r0 = threadIdx.x / PC_NB, cc = threadIdx.x - r0 * PC_NB;
-    double mine[4];
+    if constexpr (PW) {
+        const int lane = threadIdx.x;
+        double blk[PC_NB / 2];
+        pc_wave_load_block(blk, lane, m, p0, nb, src, base);
+        pc_invert_block_wave(blk, lane, nb);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r = r0 + 8 * q;
-        mine[q] = (r < nb && cc < nb) ? src[base + (size_t)(p0 + r) * m + (p0 + cc)] : ((r == cc) ? 1.0 : 0.0);
-        ab[0][r][cc] = mine[q];
+        for (int q = 0; q < PC_NB / 2; ++q) pinv[((size_t)tr * PC_NB + 16 * (lane >> 5) + q) * PC_NB + (lane & 31)] = blk[q];
+    } else {
+        __shared__ double ab[2][PC_NB][PC_NB + 1];
+        const int r0 = threadIdx.x / PC_NB, cc = threadIdx.x - r0 * PC_NB;
+        double mine[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = r0 + 8 * q;
+            mine[q] = (r < nb && cc < nb) ? src[base + (size_t)(p0 + r) * m + (p0 + cc)] : ((r == cc) ? 1.0 : 0.0);
+            ab[0][r][cc] = mine[q];
+        }
+        __syncthreads();
+        pc_invert_block(ab, mine, r0, cc, nb);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pinv[((size_t)tr * PC_NB + r0 + 8 * q) * PC_NB + cc] = mine[q];
     }
-    __syncthreads();
-    pc_invert_block(ab, mine, r0, cc, nb);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) pinv[((size_t)tr * PC_NB + r0 + 8 * q) * PC_NB + cc] = mine[q];
 }
 
+template <int PW>
 __global__ void __launch_bounds__(256) k_pc_gj_step(int m, int p0, int nb, const double* __restrict__ src, double* __restrict__ dst,
                                                     const double* __restrict__ pinv_in, double* __restrict__ pinv_out) {
     __shared__ double sr[PC_NB][64 + 1];         // R[:, c]
@@ -608,16 +701,31 @@ __global__ void __launch_bounds__(256) k_pc_gj_step(int m, int p0, int nb, const
                 }
                 if (my_quadrant) ab[0][il][cl] = val;
             }
-    if (!owns_next) return;
-    // ---- the next step's pivot block, inverted here (k_pc_gj_rows' elimination, once instead of by every workgroup)
-    __syncthreads();
-    double mine[4];
+    if constexpr (PW) {
+        // ---- option "pc_pivot_wave": the wave that holds the next pivot block (MFMA layout) takes it through the staging LDS
+        // once, into the layout of pc_invert_block_wave, and inverts it in registers; the other waves are done.  No barrier
+        // from here on: the wave reads what the wave wrote
+        if (!my_quadrant) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        double blk[PC_NB / 2];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) mine[q] = ab[0][r0 + 8 * q][cc];
-    __syncthreads();
-    pc_invert_block(ab, mine, r0, cc, nb1);
+        for (int q = 0; q < PC_NB / 2; ++q) blk[q] = ab[0][16 * (l >> 5) + q][l & 31];
+        pc_invert_block_wave(blk, l, nb1);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) pinv_out[((size_t)tr * PC_NB + r0 + 8 * q) * PC_NB + cc] = mine[q];
+        for (int q = 0; q < PC_NB / 2; ++q) pinv_out[((size_t)tr * PC_NB + 16 * (l >> 5) + q) * PC_NB + (l & 31)] = blk[q];
+    } else {
+        if (!owns_next) return;
+        // ---- the next step's pivot block, inverted here (k_pc_gj_rows' elimination, once instead of by every workgroup)
+        __syncthreads();
+        double mine[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mine[q] = ab[0][r0 + 8 * q][cc];
+        __syncthreads();
+        pc_invert_block(ab, mine, r0, cc, nb1);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pinv_out[((size_t)tr * PC_NB + r0 + 8 * q) * PC_NB + cc] = mine[q];
+    }
 }
 
 // Dense mat-vec of the block substitution for even m: 16-byte loads, the whole row of a wave requested at once
@@ -1143,8 +1251,13 @@ int pc_gj_invert(nk2d_ctx* c, Precond* pc, int nsys) {
     const size_t mm = (size_t)pc->m * pc->m;
     const int m = pc->m;
     int src = 0;
+    // (option "pc_pivot_wave": read here, at every round of a set-up; the wave flavours compute the bits of the others.
+    // Measured at m = 1248: k_pc_pivot_invert 13.2 -> 12.7 us, k_pc_gj_rows 16.7 -> 15.0 us, k_pc_gj_step 29.6 -> 29.9 us --
+    // the fused step had the inversion hidden already: profiles/r13_pc_pivot_wave.log)
+    const int pw = c->pc_pivot_wave ? 1 : 0;
     for (int p0 = 0; p0 < m; p0 += PC_NB) {
         const int nbk = std::min(PC_NB, m - p0);
+        c->pc_pivot_wave_steps += pw;
         const double* from = pc->BUF + (size_t)src * nsys * mm;
         double* to = pc->BUF + (size_t)(1 - src) * nsys * mm;
         // (measured, set-up of iage: 416 x 416 0.529 -> 0.496 s, 208 x 208 0.088 -> 0.096 s, 104 x 104 0.022 -> 0.024 s --
@@ -1154,15 +1267,25 @@ int pc_gj_invert(nk2d_ctx* c, Precond* pc, int nsys) {
             // (the first pivot block's inverse by a launch of its own, the others by the step before)
             double* pin = pc->PINV + (size_t)((p0 / PC_NB) & 1) * nsys * PC_NB * PC_NB;
             double* pout = pc->PINV + (size_t)(1 - ((p0 / PC_NB) & 1)) * nsys * PC_NB * PC_NB;
-            if (p0 == 0)
-                hipLaunchKernelGGL(k_pc_pivot_invert, dim3(1, 1, nsys), dim3(256), 0, nk2d_s(c), m, 0, nbk, from, pin);
-            hipLaunchKernelGGL(k_pc_gj_step, dim3((m + 63) / 64, (m + 63) / 64, nsys), dim3(256), 0, nk2d_s(c), m, p0, nbk, from, to,
-                               (const double*)pin, pout);
+            const dim3 grd((m + 63) / 64, (m + 63) / 64, nsys);
+            if (pw) {
+                if (p0 == 0)
+                    hipLaunchKernelGGL(k_pc_pivot_invert<1>, dim3(1, 1, nsys), dim3(64), 0, nk2d_s(c), m, 0, nbk, from, pin);
+                hipLaunchKernelGGL(k_pc_gj_step<1>, grd, dim3(256), 0, nk2d_s(c), m, p0, nbk, from, to, (const double*)pin, pout);
+            } else {
+                if (p0 == 0)
+                    hipLaunchKernelGGL(k_pc_pivot_invert<0>, dim3(1, 1, nsys), dim3(256), 0, nk2d_s(c), m, 0, nbk, from, pin);
+                hipLaunchKernelGGL(k_pc_gj_step<0>, grd, dim3(256), 0, nk2d_s(c), m, p0, nbk, from, to, (const double*)pin, pout);
+            }
             src = 1 - src;
             continue;
         }
-        hipLaunchKernelGGL(k_pc_gj_rows, dim3((m + 255) / 256, nbk, nsys), dim3(256), 0, nk2d_s(c), m, p0, nbk, from,
-                           pc->ROWS);
+        if (pw)
+            hipLaunchKernelGGL(k_pc_gj_rows<1>, dim3((m + 255) / 256, nbk, nsys), dim3(256), 0, nk2d_s(c), m, p0, nbk, from,
+                               pc->ROWS);
+        else
+            hipLaunchKernelGGL(k_pc_gj_rows<0>, dim3((m + 255) / 256, nbk, nsys), dim3(256), 0, nk2d_s(c), m, p0, nbk, from,
+                               pc->ROWS);
         if (c->pc_valu)
             hipLaunchKernelGGL(k_pc_gj_update, dim3((m + 63) / 64, (m + 63) / 64, nsys), dim3(256), 0, nk2d_s(c), m, p0,
                                nbk, from, pc->ROWS, to);
@@ -1206,7 +1329,7 @@ int precond_eliminate_ends(nk2d_ctx* c) {
     auto above = [&](int j) -> const double* {
         return (j >= nb - 1) ? nullptr : pc->fp32 ? pc->PREV + (size_t)nsys * mm : pc->SINV + (size_t)(j + 1) * mm;
     };
-    c->pc_setup_rounds = 0;
+    c->pc_setup_rounds = c->pc_pivot_wave_steps = 0;
     for (int s = 0; s <= jm; ++s) {
         const int jl = s, jr = nb - 1 - s;
         const bool meet = s == jm, pair = !meet && jr > jm;
@@ -1236,7 +1359,7 @@ int precond_eliminate(nk2d_ctx* c) {
     PcDev D = make_pcdev(c, pc);
     const int m = pc->m;
     const dim3 blk(256), grd((m + 255) / 256, m, nsys);
-    c->pc_setup_rounds = 0;
+    c->pc_setup_rounds = c->pc_pivot_wave_steps = 0;
     for (int j = 0; j < pc->nb; ++j) {
         // the Schur inverse of the column before: inside SINV ([nsys][nb][m][m]), or -- single precision storage -- the
         // double precision copy kept of that one column ([nsys][m][m])
