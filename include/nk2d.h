@@ -250,7 +250,14 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    where all its workgroups are resident, otherwise the year routes on as without the option; 2: as 1, and where that flavour is
    not resident the same kernel within 256 registers (two waves to a SIMD, five to eight levels per lane) if that one is; 3: the
    256-register flavour wherever it exists; any value outside 0 ... 3 is an error; one and two levels per lane stay out: the
-   by-column workgroup does not exist there and a four-wave team cannot hold three coupled tracers; other modules are unaffected).
+   by-column workgroup does not exist there and a four-wave team cannot hold three coupled tracers; other modules are unaffected;
+   "frozen_phosphorus_shallow" (environment NK2D_FROZEN_PHOSPHORUS_SHALLOW), 0, default, or 1, opt-in, read at every frozen year:
+   with 1 a module_kind 1 context at ONE and TWO levels per lane (up to 128 depth levels: the grids the model is shipped with) takes
+   the one-launch year too, where "frozen_phosphorus" is non-zero and "frozen_cache_lean" is 1 or 2 -- the same workgroup of one
+   ypos column with its tracers, a wave each and never a team, nothing of the year in LDS, the one-wave flavour whatever the value of
+   "frozen_phosphorus"; everything else as at three to eight levels per lane; with 0 every year of every context takes the path it
+   takes without the option; the option changes no bit of a year, so the schedule fingerprint does not take it in; any other value
+   is an error).
    Same device functions, bit-identical results; a year that does not pass the Newton check, or a
    barrier that times out, is handed to the launch-per-phase path.  Counters by name: "frozen_persistent_years",
    "frozen_team_years" (of them: a four-wave team per column), "frozen_cache_bytes",
@@ -266,6 +273,9 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    and in "frozen_lean_years" where lean),
    "frozen_phosphorus_years" (one-launch years of the phosphorus module, option "frozen_phosphorus"; also counted in
    "frozen_persistent_years" and "frozen_lean_years"), "frozen_two_waves_years" (of them: the years that ran the 256-register flavour),
+   "frozen_phosphorus_shallow_years" (one-launch years only option "frozen_phosphorus_shallow" made possible: phosphorus at one and
+   two levels per lane; also counted in "frozen_phosphorus_years", "frozen_persistent_years" and "frozen_lean_years", never in
+   "frozen_team_years" or "frozen_two_waves_years"),
    "frozen_cache_builds", "frozen_fallbacks", "frozen_resumes"; of the host-side controller: "spec_launches_dropped",
    "spec_front_launches_dropped", "err_estimates_queued", "err_estimates_dropped" (work queued ahead of a verdict); of the
    preconditioner (option "pc_two_ended"): "pc_setup_rounds" (dependent inversion rounds of the last block elimination: ny,

@@ -250,6 +250,13 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
         c->frozen_phosphorus = (int)value;
         return 0;
     }
+    if (key == "frozen_phosphorus_shallow") {
+        // ... at one and two levels per lane too (nk2d_frozen.hip: the same by-column workgroup, nothing of the year in LDS).  Taken at
+        // the next frozen year
+        if (value != 0.0 && value != 1.0) return nk2d_fail(c, "nk2d_set_option: frozen_phosphorus_shallow is 0 or 1");
+        c->frozen_phosphorus_shallow = (int)value;
+        return 0;
+    }
     if (key == "frozen_cache_piece_mb") {
         if (!(value > 0.0) || !std::isfinite(value)) return nk2d_fail(c, "nk2d_set_option: frozen_cache_piece_mb must be > 0");
         c->frozen_cache_piece_mb = value;
@@ -630,6 +637,8 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_forced = 0;
     c->frozen_forced_years = 0;
     c->frozen_phosphorus = 0;
+    c->frozen_phosphorus_shallow = 0;
+    c->frozen_phosphorus_shallow_years = 0;
     c->frozen_two_waves_last = 0;
     c->frozen_phosphorus_years = c->frozen_two_waves_years = 0;
     c->frozen_cache_piece_allocs = c->frozen_cache_early_requests = 0;
@@ -1188,6 +1197,7 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_lean_years") v = c->frozen_lean_years;
     else if (key == "frozen_forced_years") v = c->frozen_forced_years;
     else if (key == "frozen_phosphorus_years") v = c->frozen_phosphorus_years;
+    else if (key == "frozen_phosphorus_shallow_years") v = c->frozen_phosphorus_shallow_years;
     else if (key == "frozen_two_waves_years") v = c->frozen_two_waves_years;
     else if (key == "frozen_cache_piece_allocs") v = nk2d_frozen_cache_piece_allocs(c);
     else if (key == "frozen_cache_early_requests") v = c->frozen_cache_early_requests;

@@ -161,6 +161,9 @@ struct nk2d_ctx {
     int64_t frozen_forced_years;      // one-launch years only that option made possible (also counted in frozen_persistent_years)
     // option "frozen_phosphorus": the one-launch year for the phosphorus module (kind 1), on the lean cache, three to eight levels per lane
     int frozen_phosphorus;            // default 0.  1: one wave per SIMD; 2: the 256-register flavour where that one is not resident; 3: it wherever it exists
+    // option "frozen_phosphorus_shallow": ... and at one and two levels per lane (the same by-column workgroup, nothing of the year in LDS)
+    int frozen_phosphorus_shallow;    // default 0, or 1
+    int64_t frozen_phosphorus_shallow_years;   // one-launch years only that option made possible (also counted in frozen_phosphorus_years)
     int frozen_two_waves_last;        // 1: the one-launch year just run was the 256-register flavour (k_frozen_persistent_w2)
     int64_t frozen_phosphorus_years;  // one-launch years of that module (also counted in frozen_persistent_years and frozen_lean_years)
     int64_t frozen_two_waves_years;   // of them: the years that ran the 256-register flavour

@@ -176,6 +176,7 @@ static FrozenPlanIn frozen_plan_in(const nk2d_ctx* c) {
     in.sms_nrec = c->d.sms_nrec; in.sink_thres = c->d.sink_thres; in.t0 = c->d.t0;
     in.frozen_persistent = c->frozen_persistent; in.frozen_persistent_max_e = c->frozen_persistent_max_e;
     in.frozen_forced = c->frozen_forced; in.frozen_phosphorus = c->frozen_phosphorus;
+    in.frozen_phosphorus_shallow = c->frozen_phosphorus_shallow;
     in.frozen_cache_lean = c->frozen_cache_lean; in.frozen_cache_pieces = c->frozen_cache_pieces;
     in.frozen_cache_piece_mb = c->frozen_cache_piece_mb; in.frozen_cache_piece_rows = c->frozen_cache_piece_rows;
     in.frozen_cache_max_gb = c->frozen_cache_max_gb; in.frozen_cache_after = c->frozen_cache_after;
@@ -378,7 +379,8 @@ static hipError_t launch_frozen(nk2d_ctx* c, bool team, dim3 grid, DevP& P, type
     return forced ? launch_frozen_e<2, 0, PIECES, LEAN>(c, grid, P, A) : launch_frozen_e<0, 0, PIECES, LEAN>(c, grid, P, A);
 }
 
-// phosphorus (option "frozen_phosphorus"): always by column and lean; `two_waves`: the 256-register entry (five to eight levels per lane)
+// phosphorus (option "frozen_phosphorus"): always by column and lean; `two_waves`: the 256-register entry (five to eight levels per lane).
+// Below three levels per lane frozen_lds_doubles() is 0: no dynamic LDS
 template <int E, int PIECES>
 static hipError_t launch_frozen_phos_one(nk2d_ctx* c, DevP& P, typename FrozenArgOf<PIECES>::type& A, bool two_waves, bool check_only) {
     const dim3 grid((unsigned)c->ny), block((unsigned)(64 * c->tc));
@@ -394,6 +396,9 @@ template <int PIECES>
 static hipError_t launch_frozen_phos(nk2d_ctx* c, DevP& P, typename FrozenArgOf<PIECES>::type& A, bool two_waves, bool check_only = false) {
     if (!A.by_column || c->tc > NK2D_WAVES_PER_BLOCK) return hipErrorInvalidValue;
     switch (c->E) {
+        // one and two levels per lane (option "frozen_phosphorus_shallow"): nothing of the year in LDS, the one-wave flavour only
+        case 1: return launch_frozen_phos_one<1, PIECES>(c, P, A, two_waves, check_only);
+        case 2: return launch_frozen_phos_one<2, PIECES>(c, P, A, two_waves, check_only);
         case 3: return launch_frozen_phos_one<3, PIECES>(c, P, A, two_waves, check_only);
         case 4: return launch_frozen_phos_one<4, PIECES>(c, P, A, two_waves, check_only);
         case 5: return launch_frozen_phos_one<5, PIECES>(c, P, A, two_waves, check_only);
@@ -727,7 +732,8 @@ static int frozen_launch_year(nk2d_ctx* c, const FrozenPlan& pl, int64_t n, DevP
     // option "frozen_team": a workgroup per column (four waves: newton_team_body) instead of a wave per column, up to two levels per
     // lane.  Measured in round 3 (profiles/r03_frozen_team.log, r03_frozen_nbsync.log): teams want a CU each and beat the
     // wave-per-column year at every such size -- 26^2 9.4 ms, 52^2 14.9, 104^2 27.0 with the neighbour hand-over.
-    const bool team = c->frozen_team && c->E <= 2;
+    // (a phosphorus year at those depths -- option "frozen_phosphorus_shallow" -- is one ypos column to a workgroup: no team)
+    const bool team = c->frozen_team && c->E <= 2 && !pl.phos;
     const dim3 grid((unsigned)(team ? c->ncol : nk2d_grid(c->ncol)));
     NK2D_CHECK(c, hipMemsetAsync(c->YR_SYNC, 0, yr_sync_bytes(c), nk2d_s(c)));
     NK2D_CHECK(c, hipMemsetAsync(c->YR_OUT, 0, sizeof(double) * 32, nk2d_s(c)));

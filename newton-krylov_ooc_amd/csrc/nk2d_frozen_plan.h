@@ -32,6 +32,7 @@ struct FrozenPlanIn {
     int sms_nrec;
     double sink_thres, t0;
     int frozen_persistent, frozen_persistent_max_e, frozen_forced, frozen_phosphorus;
+    int frozen_phosphorus_shallow;
     int frozen_cache_lean, frozen_cache_pieces;
     double frozen_cache_piece_mb;
     int64_t frozen_cache_piece_rows;
@@ -59,10 +60,11 @@ static inline bool frozen_thres(const FrozenPlanIn& in) { return in.kind == 2 &&
 
 // phosphorus (module_kind 1) where option "frozen_phosphorus" lets it take the one-launch year: on the lean cache ("frozen_cache_lean" 1, or
 // 2, which for such a context always means lean), at three to eight levels per lane -- the workgroup is then one ypos column with
-// its tracers, a wave each.  One and two levels per lane stay out: the by-column workgroup does not exist there, and the
-// four-wave teams cannot hold three coupled tracers
+// its tracers, a wave each.  One and two levels per lane come in with option "frozen_phosphorus_shallow" only: the same by-column
+// workgroup with nothing of the year in LDS (the four-wave teams of those depths cannot hold three coupled tracers: no team there)
 static inline bool frozen_phos(const FrozenPlanIn& in) {
-    return in.kind == 1 && in.frozen_phosphorus != 0 && in.frozen_cache_lean != 0 && in.E >= 3 && in.E <= 8 && in.tc <= NK2D_WAVES_PER_BLOCK;
+    const int e_min = in.frozen_phosphorus_shallow != 0 ? 1 : 3;
+    return in.kind == 1 && in.frozen_phosphorus != 0 && in.frozen_cache_lean != 0 && in.E >= e_min && in.E <= 8 && in.tc <= NK2D_WAVES_PER_BLOCK;
 }
 
 static inline size_t frozen_ntab(const FrozenPlanIn& in) { return (size_t)in.ncol * NK2D_TAB * 64; }
@@ -321,7 +323,7 @@ static inline void frozen_lds_shape(const FrozenPlanIn& in, bool phos, bool lean
     // (phosphorus: its tracers are coupled inside a ypos column -- by column whatever the two options say, "frozen_coef_lds" 0 included)
     if (phos) by_column = 1;
     if (!by_column) coef_lds &= 3;
-    const bool team = in.frozen_team && in.E <= 2;
+    const bool team = in.frozen_team && in.E <= 2 && !phos;     // (a phosphorus year is never a team)
     if (!by_column || phos || (coef_lds & 15) != 15 || !NK2D_FROZEN_OWN(in.E, in.kind, team, lean)) coef_lds &= 15;
     const int nw = by_column ? in.tc : std::max(1, std::min(NK2D_WAVES_PER_BLOCK, in.frozen_wpb));
     const int wgs = by_column ? in.ny : (in.ncol + nw - 1) / nw;

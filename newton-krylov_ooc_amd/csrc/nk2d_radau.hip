@@ -1189,6 +1189,8 @@ int run_replay(Ctl& s, const double* sched, int64_t n, bool check) {
                 if (c->kind == 2 && (c->E > 4 || (c->d.sms_nrec > 0 && c->d.sink_thres > 0.0))) c->frozen_forced_years++;
                 // (phosphorus: option "frozen_phosphorus" let it in; of those years, the ones that ran the 256-register flavour)
                 if (c->kind == 1) { c->frozen_phosphorus_years++; c->frozen_two_waves_years += c->frozen_two_waves_last; }
+                // (... at one and two levels per lane: option "frozen_phosphorus_shallow" let it in)
+                if (c->kind == 1 && c->E <= 2) c->frozen_phosphorus_shallow_years++;
                 return 0;
             }
             return 3;

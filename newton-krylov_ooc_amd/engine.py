@@ -231,6 +231,9 @@ class ModuleEngine:
         # 2 the 256-register flavour where that one is not resident, 3 that flavour wherever it exists (csrc/nk2d_frozen.hip)
         if "NK2D_FROZEN_PHOSPHORUS" in os.environ:
             self.set_option("frozen_phosphorus", float(os.environ["NK2D_FROZEN_PHOSPHORUS"]))
+        # ... and at one and two levels per lane too (the grids the model is shipped with), where "frozen_phosphorus" is set
+        if "NK2D_FROZEN_PHOSPHORUS_SHALLOW" in os.environ:
+            self.set_option("frozen_phosphorus_shallow", float(os.environ["NK2D_FROZEN_PHOSPHORUS_SHALLOW"]))
         # the one-launch frozen year's norm partials out of the way of the hand-over between workgroups (csrc/nk2d_frozen_body.inc)
         if "NK2D_FROZEN_EARLY" in os.environ:
             self.set_option("frozen_early", float(os.environ["NK2D_FROZEN_EARLY"]))
