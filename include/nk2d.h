@@ -267,6 +267,8 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    "frozen_lean_years" (one-launch years run on a lean cache; also counted in "frozen_persistent_years"),
    "frozen_lds_bits" (the bits of option "frozen_coef_lds" in effect in the one-launch year launched last, after fitting),
    "frozen_early_bits" (option "frozen_early" as in effect in that year: 0 wherever "frozen_lds_bits" lacks 16 and 32),
+   "frozen_stage_exchange_bits" (option "frozen_stage_exchange" as in effect in that year, under the same rule -- and 0 whatever the
+   option says for linear sources at seven levels per lane on a cache in pieces, whose kernel has no body for it),
    "frozen_step_sums_hash" (64-bit FNV-1a hash of the bits of the step sums the last whole-year check of a frozen year read: the
    norm sums of every step's last Newton iteration and of the one before -- the same for the same year by whatever path),
    "frozen_forced_years" (one-launch years only option "frozen_forced" made possible; also counted in "frozen_persistent_years",
@@ -481,6 +483,12 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    launched last ran with), "frozen_early" (1, default, or 0: a wave that carries the whole own state -- "frozen_lds_bits" 63 --
    forms the norm partial of an update part behind that part's stores, while they are on their way, and stores it behind its
    hand-over flag instead of in front of the stores its neighbours wait for; the same operations; counter "frozen_early_bits"),
+   "frozen_stage_exchange" (1, default, or 0: the waves that carry the whole own state publish the stage values U_i = Y + Z_i of
+   their column in place of Z_i, and a stage part takes its neighbours' three columns from there with no load of their Y and no
+   addition, its own from its registers: 14 of a stage phase's 56 loads over the fabric go; the same operands in the same
+   addition, on the producing side: the same bits; Z goes to memory only in the rows with an error estimate and in the last;
+   not on a cache in pieces with linear sources at seven levels per lane, which stays on the body without it;
+   counter "frozen_stage_exchange_bits"),
    "frozen_sums_poison" (0, default, or 1; for tests: the rows of norm partials are filled with NaN before every frozen year, so
    that a partial the year does not store fails its check instead of passing on what an earlier year left there),
    "frozen_by_column" (1,

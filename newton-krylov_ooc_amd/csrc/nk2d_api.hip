@@ -193,6 +193,7 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
     if (key == "frozen_coef_lds") { c->frozen_coef_lds = (int)value & 63; return 0; }
     if (key == "frozen_sums_poison") { c->frozen_sums_poison = (int)value != 0 ? 1 : 0; return 0; }
     if (key == "frozen_early") { c->frozen_early = (int)value != 0 ? 1 : 0; return 0; }
+    if (key == "frozen_stage_exchange") { c->frozen_stage_exchange = (int)value != 0 ? 1 : 0; return 0; }
     if (key == "frozen_by_column") { c->frozen_by_column = (int)value; return 0; }
     if (key == "frozen_cache_after") { c->frozen_cache_after = (int)value; return 0; }
     if (key == "spec_bias") { c->spec_bias = value > 0.0 ? value : 1.0; return 0; }
@@ -646,6 +647,8 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_lds_bits = 0;
     c->frozen_early = NK2D_FROZEN_EARLY_DEFAULT;
     c->frozen_early_bits = 0;
+    c->frozen_stage_exchange = NK2D_FROZEN_STAGE_EXCHANGE_DEFAULT;
+    c->frozen_stage_exchange_bits = 0;
     c->frozen_by_column = 1;
     c->strm = nullptr;
     c->spec_bias = 1.0;
@@ -1193,6 +1196,7 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_cache_lean") v = nk2d_frozen_cache_is_lean(c);
     else if (key == "frozen_lds_bits") v = c->frozen_lds_bits;
     else if (key == "frozen_early_bits") v = c->frozen_early_bits;
+    else if (key == "frozen_stage_exchange_bits") v = c->frozen_stage_exchange_bits;
     else if (key == "frozen_step_sums_hash") v = c->frozen_step_sums_hash;
     else if (key == "frozen_lean_years") v = c->frozen_lean_years;
     else if (key == "frozen_forced_years") v = c->frozen_forced_years;

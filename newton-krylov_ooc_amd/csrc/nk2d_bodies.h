@@ -893,6 +893,7 @@ __device__ __forceinline__ void w_lds_put(double* s, int r, int lane, const doub
 //   bit 5  z   : the column's own three stage values stay in the wave's registers from the update part of one phase to the
 //                stage part of the next (OwnState::z)
 //   bit 7  norm : the update part may form the norm partial behind its stores and leave it to the caller to store (LateNorm)
+//   bit 8  xchg : the neighbours exchange stage values U_i = Y + Z_i instead of Z_i and Y (StageXchg; on top of bits 4 and 5)
 struct LdsSrc {
     const double* coef;
     double* w;
@@ -924,6 +925,23 @@ struct LateNorm {
     double acc;
     double* part;
     int defer, pending;
+#ifdef NK2D_FROZEN_CLOCKS
+    // probe build only: ticks between the hand-over's poll match (`ck_match`, set by the caller) and the moment the neighbours'
+    // columns of the stage part are in registers -- three counted waits, one behind each stage's loads, the first from the match
+    long long ck_match = 0, ck_fetch = 0;
+#endif
+};
+// The neighbours exchange stage values (CL bit 8; option "frozen_stage_exchange" of the one-launch year).  A stage part uses a
+// neighbour's Y and Z_i only as the sum U_i = Y + Z_i -- the sum that neighbour forms for its own column one phase later.  So the
+// update part forms u_i = y + z_i (y: the LDS copy) where it has just computed z_i, stores it write-through to `uout` in place
+// of z_i and keeps it in OwnState::z; the stage part takes its own column from there with no addition and the neighbours'
+// three columns from `u` with no load of their Y and no addition: the same operands in the same IEEE addition, on the
+// producing side.  Z itself goes to memory only where something reads it from there (`keep_z`: the rows with an error
+// estimate and the year's last row).  Every access to `u` / `uout` is the MP = 1 accessor.
+struct StageXchg {
+    const double* u;    // what the stage part reads: [3][nv]
+    double* uout;       // where the update part (FINAL: the prediction of the next attempt) stores: [3][nv]
+    int keep_z;         // the update part stores Z too
 };
 // sum over the wave of the squared scaled increments (radau.py:113-129): the expressions of the update part of newton_fused_body
 template <int E>
@@ -942,7 +960,9 @@ __device__ __forceinline__ double norm_partial_sum(const DevP& P, const double (
 template <int E, int KIND, int FACTOR, int STAGE, int MP = 0, int FINAL = 0, int CL = 0>
 __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs& A, int task, int lane,
                                                   const FinalArgs* fin = nullptr, const LdsSrc* lds = nullptr,
-                                                  OwnState<E>* own = nullptr, LateNorm* late = nullptr) {
+                                                  OwnState<E>* own = nullptr, LateNorm* late = nullptr,
+                                                  const StageXchg* xc = nullptr) {
+    static_assert(!(CL & 256) || (CL & 48) == 48, "the stage-value exchange needs the column's whole own state");
     const double* coef_lds = (CL & 1) ? lds->coef : nullptr;
     double* w_lds = (CL & 2) ? lds->w : nullptr;
     (void)coef_lds; (void)w_lds;
@@ -954,6 +974,13 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         if constexpr (CL & 1) load_coef_lds<E>(coef_lds, lane, cf);       // (the wave's own column: stored there at kernel entry)
         else load_coef<E>(P, j, lane, cf);
         double y0[E], ys[E], yn[E];
+        if constexpr (CL & 256) {
+            // (the stage values come with Y in them: Y only where the LDS copy, which the update part reads, has to be refilled)
+            if (!own->valid) {
+                load_col<E, MP>(A.st.y, task, lane, y0);
+                w_lds_put<E>(lds->y, 0, lane, y0);
+            }
+        } else {
         if constexpr (CL & 16) {
             if (!own->valid) {      // (Y was written by another path: from memory, and into the LDS copy)
                 load_col<E, MP>(A.st.y, task, lane, y0);
@@ -966,11 +993,26 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         }
         load_col<E, MP>(A.st.y, cs_col, lane, ys);
         load_col<E, MP>(A.st.y, cn_col, lane, yn);
+        }
 #pragma unroll
         for (int e = 0; e < E; ++e) { fr[e] = 0.0; fcr[e] = 0.0; fci[e] = 0.0; }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             double c[E], cs[E], cn[E], kv[E], f[E];
+#ifdef NK2D_FROZEN_CLOCKS
+            long long ck_t0 = 0;
+            if constexpr (CL & 128) ck_t0 = (i == 0) ? late->ck_match : (long long)__builtin_amdgcn_s_memrealtime();
+#endif
+            if constexpr (CL & 256) {
+                if (own->valid) {   // (u_i as the update part of the phase before formed it)
+#pragma unroll
+                    for (int e = 0; e < E; ++e) c[e] = own->z[i][e];
+                } else {            // (the start of the year, and behind the end of a step with an error estimate)
+                    load_col<E, 1>(xc->u + i * A.st.nv, task, lane, c);
+                }
+                load_col<E, 1>(xc->u + i * A.st.nv, cs_col, lane, cs);
+                load_col<E, 1>(xc->u + i * A.st.nv, cn_col, lane, cn);
+            } else {
             if constexpr (CL & 32) {
                 if (own->valid) {   // (what the update part of the phase before stored to A.st.z for the others)
 #pragma unroll
@@ -983,10 +1025,19 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
             }
             load_col<E, MP>(A.st.z + i * A.st.nv, cs_col, lane, cs);
             load_col<E, MP>(A.st.z + i * A.st.nv, cn_col, lane, cn);
+            }
+#ifdef NK2D_FROZEN_CLOCKS
+            if constexpr (CL & 128) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                late->ck_fetch += (long long)__builtin_amdgcn_s_memrealtime() - ck_t0;
+            }
+#endif
             if constexpr (CL & 4) col_lds_get<E>(lds->step, i, lane, kv);
             else load_col<E, MP>(A.st.kv[i], j, lane, kv);
+            if constexpr (!(CL & 256)) {
 #pragma unroll
             for (int e = 0; e < E; ++e) { c[e] = y0[e] + c[e]; cs[e] = ys[e] + cs[e]; cn[e] = yn[e] + cn[e]; }
+            }
             tend_col<E, KIND>(P, cf, c, cs, cn, kv, tr, lane, f);
             if constexpr (KIND == 2) forced_sources<E>(P, A.st.kv[i], j, lane, c, f);
             if constexpr (KIND == 1) {
@@ -1179,7 +1230,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
     // the wave and -- where the end of the step does not need it -- the state column are then left out
     const bool norm = A.part != nullptr;
     double yy[E], w0[E], w1[E], w2[E];
-    if (FINAL || norm) {
+    if (FINAL || norm || (CL & 256) != 0) {     // (xchg: u_i = y + z_i is formed below)
         if constexpr (CL & 16) col_lds_get<E>(lds->y, 0, lane, yy);
         else load_col<E, MP>(A.st.y, task, lane, yy);
     }
@@ -1237,8 +1288,21 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
                 o[i][e] = v - yn[e];
             }
         }
+        if constexpr (CL & 256) {
+            // (the next attempt's u_i = y_new + z_i for the neighbours and for the wave itself; nothing reads this Z from memory)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                double uu[E];
+#pragma unroll
+                for (int e = 0; e < E; ++e) uu[e] = yn[e] + o[i][e];
+                store_col<E, 1>(xc->uout + i * A.st.nv, task, lane, uu);
+#pragma unroll
+                for (int e = 0; e < E; ++e) own->z[i][e] = uu[e];
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < 3; ++i) store_col<E, MP>(fin->znext + i * A.st.nv, task, lane, o[i]);
+        }
         double wv[E];
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -1247,7 +1311,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
             if constexpr (CL & 2) w_lds_put<E>(w_lds, r, lane, wv);
             else store_col<E>(wout + r * A.st.nv, task, lane, wv);
         }
-        if constexpr (CL & 32) {
+        if constexpr ((CL & 32) != 0 && (CL & 256) == 0) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -1273,8 +1337,20 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
     for (int r = 0; r < 3; ++r) {
 #pragma unroll
         for (int e = 0; e < E; ++e) zz[e] = (cT[r][0] * w0[e] + cT[r][1] * w1[e]) + cT[r][2] * w2[e];
+        if constexpr (CL & 256) {
+            // (u_r = y + z_r is what the neighbours and the wave's own next stage part take; Z where this row's estimate, the end
+            // of its step or the caller's commit reads it from memory)
+            double uu[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) uu[e] = yy[e] + zz[e];
+            store_col<E, 1>(xc->uout + r * A.st.nv, task, lane, uu);
+            if (xc->keep_z) store_col<E, MP>(zout + r * A.st.nv, task, lane, zz);
+#pragma unroll
+            for (int e = 0; e < E; ++e) own->z[r][e] = uu[e];
+        } else {
         store_col<E, MP>(zout + r * A.st.nv, task, lane, zz);
-        if constexpr (CL & 32) {
+        }
+        if constexpr ((CL & 32) != 0 && (CL & 256) == 0) {
 #pragma unroll
             for (int e = 0; e < E; ++e) own->z[r][e] = zz[e];
         }
@@ -2036,6 +2112,10 @@ static inline void fill_fused_args(nk2d_ctx* c, FusedArgs& A, bool do_stage, boo
 // Synchronisation block of the one-launch frozen year: abort flag at 4096, from 8192 one 128-byte line per workgroup
 // for NeighbourSync.
 static inline size_t yr_sync_bytes(const nk2d_ctx* c) { return 8192 + (size_t)c->ncol * 128; }
+// Behind it, in the same allocation, the two buffers of the stage-value exchange (StageXchg): U, then UN, [3][nv] doubles each.
+// Only the block in front is cleared before a year: the year stores every column of U before anything reads it.
+__host__ __device__ static inline size_t yr_xchg_offset(int ncol) { return 8192 + (size_t)ncol * 128; }
+static inline size_t yr_xchg_bytes(const nk2d_ctx* c) { return sizeof(double) * 6 * c->nv; }
 
 // Where a workgroup is ONE column (the team flavour of k_frozen_persistent) the grid barrier asks for more than the data
 // flow needs: a column reads what its two lateral neighbours (same tracer) wrote in the phase before, and nothing else of
@@ -2056,6 +2136,7 @@ struct NeighbourSync {
     // probe build only: ticks of s_memrealtime (100 MHz) wave 0 of a workgroup spent (a) draining its stores in publish(),
     // (b) between its flag store and the poll's match -- whatever the caller does in between included
     long long ck_drain = 0, ck_wait = 0, ck_flag = 0;
+    long long ck_match = 0;     // when the last poll ended (every wave's own clock: read behind the workgroup's join)
 #endif
     // The hand-over in two halves, for a caller that has work of its own column to do while the neighbours catch up.
     // publish(): every wave's write-through stores drained, the workgroup joined, the flag stored.  wait(): the bounded poll
@@ -2108,6 +2189,9 @@ struct NeighbourSync {
 #endif
         }
         __syncthreads();
+#ifdef NK2D_FROZEN_CLOCKS
+        ck_match = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
         if (fences) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         return *lds_ok != 0;
     }
@@ -2144,6 +2228,9 @@ struct NeighbourSync {
             if (lane == 0) *lds_ok = good;
         }
         __syncthreads();
+#ifdef NK2D_FROZEN_CLOCKS
+        ck_match = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
         if (fences) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         return *lds_ok != 0;
     }
@@ -2405,6 +2492,10 @@ struct FrozenArgs {
                                  // Every other reader -- the kernel's `& bit` and non-zero tests, frozen_factor_phase(), frozen_lds_doubles()
                                  // -- looks at single bits below 64 or at "any bit set", and bit 8 is never set alone: it changes none of them
 #define NK2D_FROZEN_EARLY_OF(coef_lds) (((coef_lds) >> 8) & 1)
+                                 // Bit 9: option "frozen_stage_exchange", under the same rule (set only on top of all six).  Its two buffers
+                                 // U and UN, [3][nv] doubles each, lie behind the synchronisation block `arrive` points to (yr_xchg_offset():
+                                 // no field of their own either)
+#define NK2D_FROZEN_XCHG_OF(coef_lds) (((coef_lds) >> 9) & 1)
     int by_column;               // 1: a workgroup is ONE ypos column with all its tracers (a wave each) instead of adjacent columns of one tracer
     // option "frozen_forced" bit 2 (forced module with a thresholded sink, lean cache): the rows' file-source planes at their Jacobian
     // times, [n][np] behind J in the slab (a cache in pieces: PieceTab::oS), and 1 where the year forms UPR from them
@@ -2447,9 +2538,11 @@ __device__ __forceinline__ void tend_at_body(const DevP& P, const double* __rest
 
 // what the step-ending launch does behind the update (FINAL in newton_fused_body), from the stage values in memory: for
 // the steps whose last Newton iteration is an ordinary one because their error estimate sits in between
-template <int E, int MP>
+// XU = 1 (the stage-value exchange, StageXchg): the next attempt's u_i = y_new + z_i go to `unext` as well, write-through
+template <int E, int MP, int XU = 0>
 __device__ __forceinline__ void step_tail_body(const double* __restrict__ y, const double* __restrict__ z, size_t nv,
-                                               const FinalArgs& fin, double* __restrict__ wout, int task, int lane) {
+                                               const FinalArgs& fin, double* __restrict__ wout, int task, int lane,
+                                               double* __restrict__ unext = nullptr) {
     double yy[E], z0[E], z1[E], z2[E], yn[E];
     load_col<E, MP>(y, task, lane, yy);
     load_col<E, MP>(z, task, lane, z0);
@@ -2475,6 +2568,15 @@ __device__ __forceinline__ void step_tail_body(const double* __restrict__ y, con
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) store_col<E, MP>(fin.znext + i * nv, task, lane, o[i]);
+    if constexpr (XU) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double uu[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) uu[e] = yn[e] + o[i][e];
+            store_col<E, 1>(unext + i * nv, task, lane, uu);
+        }
+    }
     double wv[E];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {

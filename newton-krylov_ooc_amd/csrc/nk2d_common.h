@@ -34,6 +34,8 @@
 
 // option "frozen_early" as a context starts with it (1: the norm partial of an update part behind its stores and the hand-over's flag)
 #define NK2D_FROZEN_EARLY_DEFAULT 1
+// option "frozen_stage_exchange" as a context starts with it (1: the neighbours of the one-launch year exchange stage values, not Z and Y)
+#define NK2D_FROZEN_STAGE_EXCHANGE_DEFAULT 1
 struct nk2d_ctx {
     nk2d_desc d;
     int nz, ny, tc, E, nzp, ncol, nreg;
@@ -145,6 +147,8 @@ struct nk2d_ctx {
     int frozen_lds_bits;  // counter "frozen_lds_bits": the bits of it in effect in the one-launch year launched last, after fitting
     int frozen_early;     // option "frozen_early": a wave of the one-launch year forms its norm partials out of the way of the hand-over
     int frozen_early_bits; // counter "frozen_early_bits": the option in effect in the one-launch year launched last
+    int frozen_stage_exchange;      // option "frozen_stage_exchange": the neighbours of the one-launch year exchange the stage values Y + Z_i, not Z_i and Y
+    int frozen_stage_exchange_bits; // counter "frozen_stage_exchange_bits": the option in effect in the one-launch year launched last
     int frozen_by_column; // option "frozen_by_column": a workgroup of the one-launch year is one ypos column with all its tracers
     int frozen_alloc_async;   // option "frozen_alloc_async": a schedule cache above 8 GB is allocated by a thread of its own
     int frozen_cache_after;   // option "frozen_cache_after": frozen years of a schedule that run launch by launch before its cache is built (default 0; -1: 0 for a cache below 8 GB, 3 above)

@@ -682,7 +682,8 @@ static int frozen_year_buffers(nk2d_ctx* c) {
     if (c->YR_OUT) return 0;
     NK2D_CHECK(c, hipMalloc((void**)&c->YR_PART, sizeof(double) * 2 * c->ncol));
     NK2D_CHECK(c, hipMalloc((void**)&c->YR_OUT, sizeof(double) * 32));
-    NK2D_CHECK(c, hipMalloc((void**)&c->YR_SYNC, yr_sync_bytes(c)));
+    // (behind the synchronisation block: U and UN of the stage-value exchange, option "frozen_stage_exchange")
+    NK2D_CHECK(c, hipMalloc((void**)&c->YR_SYNC, yr_sync_bytes(c) + yr_xchg_bytes(c)));
     NK2D_CHECK(c, hipMalloc((void**)&c->YR_MTAB, sizeof(int) * std::max<size_t>(c->rho_tab.size(), 1)));
     NK2D_CHECK(c, hipHostMalloc((void**)&c->hYR_OUT, sizeof(double) * 32));
     NK2D_CHECK(c, hipEventCreate(&c->yr_ev[0]));
@@ -724,6 +725,12 @@ static int frozen_year_args(nk2d_ctx* c, const nk2d_frozen_cache* fc, const Froz
     // (invariant: bit 8 only together with bits 0 - 5.  Everything that takes A.coef_lds from here on -- frozen_lds_doubles() in the
     // launch functions, the kernel -- tests bits below 64 or non-zero, which bit 8 on top of 63 does not change)
     A.coef_lds |= c->frozen_early_bits << 8;
+    // option "frozen_stage_exchange", bit 9, under the same rule.  It changes no decision: not part of the schedule fingerprint
+    // (and only in the instantiations that have the body for it: NK2D_FROZEN_XCHG)
+    const bool team_year = c->frozen_team && c->E <= 2 && !pl.phos;
+    c->frozen_stage_exchange_bits =
+        ((A.coef_lds & 48) == 48 && NK2D_FROZEN_XCHG(c->E, c->kind, team_year, pl.pieces, pl.lean)) ? c->frozen_stage_exchange : 0;
+    A.coef_lds |= c->frozen_stage_exchange_bits << 9;
     return 0;
 }
 
@@ -760,8 +767,10 @@ static int frozen_launch_year(nk2d_ctx* c, const FrozenPlan& pl, int64_t n, DevP
     const double* o = c->hYR_OUT;
     if ((int)o[0] != 0 || (int64_t)o[1] != n) return 2;
 #ifdef NK2D_FROZEN_CLOCKS
-    std::fprintf(stderr, "frozen clocks (early %d): %.0f phases, per phase drain %.3f us, flag store to poll match %.3f us, rest %.3f us; kernel %.3f ms\n",
-                 c->frozen_early_bits, o[11], 0.01 * o[8] / o[11], 0.01 * o[9] / o[11], 0.01 * (o[10] - o[8] - o[9]) / o[11], 1.0e-5 * o[10]);
+    std::fprintf(stderr, "frozen clocks (early %d, stage exchange %d): %.0f phases, per phase drain %.3f us, flag store to poll match %.3f us, "
+                 "poll match to neighbours loaded %.3f us, rest %.3f us; kernel %.3f ms\n",
+                 c->frozen_early_bits, c->frozen_stage_exchange_bits, o[11], 0.01 * o[8] / o[11], 0.01 * o[9] / o[11], 0.01 * o[12] / o[11],
+                 0.01 * (o[10] - o[8] - o[9] - o[12]) / o[11], 1.0e-5 * o[10]);
 #endif
     if (team) c->frozen_team_years++;
     // the launch itself, between two events on the context's stream (bench.py's roofline of the one-launch year)

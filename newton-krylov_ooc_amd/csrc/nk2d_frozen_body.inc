@@ -109,11 +109,29 @@
     // forms the norm partial of an update part behind that part's stores and stores it behind the hand-over's flag (LateNorm)
     LateNorm late = {0.0, nullptr, (OWN && by_col && own_bits == 48) ? uni_i(NK2D_FROZEN_EARLY_OF(A.coef_lds)) : 0, 0};
     (void)late;
+    // option "frozen_stage_exchange" (bit 9 of A.coef_lds, under the same rule): the neighbours exchange the stage values U_i = Y + Z_i,
+    // not Z_i and Y (StageXchg).  U and UN lie behind the synchronisation block; their parity is Z's and ZN's (swapZ)
+    constexpr bool XCHG = OWN && NK2D_FROZEN_XCHG(E, KIND, TEAM, PIECES, LEAN);     // (compiled in where it costs no spilled register)
+    const int xchg = (XCHG && by_col && own_bits == 48) ? uni_i(NK2D_FROZEN_XCHG_OF(A.coef_lds)) : 0;
+    double* const xu0 = XCHG ? (double*)((char*)A.arrive + yr_xchg_offset(P.ncol)) : nullptr;
+    (void)xchg; (void)xu0;
+#define FZ_U (swapZ ? xu0 + 3 * nv : xu0)
+#define FZ_UN (swapZ ? xu0 : xu0 + 3 * nv)
     // first attempt of the year: Z0 = 0, W0 = 0 (radau.py:445-446)
     if (col_wave && (!TEAM || tw == 0)) {
         double zero[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) zero[e] = 0.0;
+        if constexpr (XCHG) {
+            if (xchg) {     // U0 = Y + Z0, by the addition itself (a -0.0 of Y comes out as the stage part's own sum gave it)
+                double y0[E];
+                load_col<E, MPX>(FZ_Y, wave, lane, y0);
+#pragma unroll
+                for (int e = 0; e < E; ++e) y0[e] = y0[e] + zero[e];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) store_col<E, 1>(FZ_U + i * nv, wave, lane, y0);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             store_col<E, MPX>(FZ_Z + i * nv, wave, lane, zero);
@@ -247,6 +265,9 @@
                         __syncthreads();
                     }
                 }
+#ifdef NK2D_FROZEN_CLOCKS
+                late.ck_match = nbs.ck_match;
+#endif
                 if (is_final) {
                     FinalArgs Fin;
                     Fin.ynew = FZ_YOLD;
@@ -269,7 +290,14 @@
                             if (m == 1) { newton_single_body<E, MPX, 1>(P, FA, wave, lane, &Fin); taken = true; }
                         }
                         if constexpr (OWN) {
-                            if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 191>(P, FA, wave, lane, &Fin, &L, &own, &late); taken = true; }
+                            if constexpr (XCHG) {
+                            if (own_bits == 48 && xchg) {
+                                const StageXchg XC = {FZ_U, do_stage ? FZ_UN : FZ_U, 0};
+                                newton_fused_body<E, KIND, 0, 1, MPX, 1, 447>(P, FA, wave, lane, &Fin, &L, &own, &late, &XC); taken = true;
+                            }
+                            }
+                            if (taken) {}
+                            else if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 191>(P, FA, wave, lane, &Fin, &L, &own, &late); taken = true; }
                             else if (!PIECES && own_bits == 32) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 47>(P, FA, wave, lane, &Fin, &L, &own); taken = true; }
                             else if (own_bits == 16) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 31>(P, FA, wave, lane, &Fin, &L, &own); FZ_OWN_DEAD() taken = true; }
                         }
@@ -301,7 +329,16 @@
                             if (m == 1) { newton_single_body<E, MPX, 0>(P, FA, wave, lane); taken = true; }
                         }
                         if constexpr (OWN) {
-                            if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 191>(P, FA, wave, lane, nullptr, &L, &own, &late); taken = true; }
+                            if constexpr (XCHG) {
+                            if (own_bits == 48 && xchg) {
+                                // (Z to memory where something reads it from there: the estimate and the end of a step that carries one,
+                                // the caller's commit of the last row)
+                                const StageXchg XC = {FZ_U, (do_stage && do_update) ? FZ_UN : FZ_U, (with_err || last_row) ? 1 : 0};
+                                newton_fused_body<E, KIND, 0, 1, MPX, 0, 447>(P, FA, wave, lane, nullptr, &L, &own, &late, &XC); taken = true;
+                            }
+                            }
+                            if (taken) {}
+                            else if (own_bits == 48) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 191>(P, FA, wave, lane, nullptr, &L, &own, &late); taken = true; }
                             else if (!PIECES && own_bits == 32) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 47>(P, FA, wave, lane, nullptr, &L, &own); taken = true; }
                             else if (own_bits == 16) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 31>(P, FA, wave, lane, nullptr, &L, &own); FZ_OWN_DEAD() taken = true; }
                         }
@@ -349,8 +386,12 @@
                 Fin.znext = FZ_ZN;
                 Fin.x0 = R.x0; Fin.x1 = R.x1; Fin.x2 = R.x2;
                 Fin.nblk_cols = 0;
-                step_tail_body<E, MPX>(FZ_Y, FZ_Z, nv, Fin, A.W, wave, lane);
-                own.valid = 0;      // (this rare phase writes Y and Z: the next stage part takes both from memory)
+                bool tail_done = false;
+                if constexpr (XCHG) {
+                    if (xchg) { step_tail_body<E, MPX, 1>(FZ_Y, FZ_Z, nv, Fin, A.W, wave, lane, FZ_UN); tail_done = true; }
+                }
+                if (!tail_done) step_tail_body<E, MPX>(FZ_Y, FZ_Z, nv, Fin, A.W, wave, lane);
+                own.valid = 0;      // (this rare phase writes Y and Z: the next stage part takes both from memory -- or Y and its own U)
                 if constexpr (COEF_LDS) {
                     if (w_in_lds) {     // (this rare phase writes W to memory: into the column's LDS copy from there)
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -384,11 +425,13 @@ finish:
     // rest -- a workgroup that gave up raised the abort flag, its neighbours give up on it in turn
     if (status != 0 && threadIdx.x == 0) A.out[0] = (double)status;
 #ifdef NK2D_FROZEN_CLOCKS
-    // probe build: wave 0 of the middle workgroup reports its three spans in spare slots of `out` (ticks of 10 ns: the store
-    // drains, flag store to poll match, the whole kernel -- the rest of the phases is the difference) and its phase count
+    // probe build: wave 0 of the middle workgroup reports its spans in spare slots of `out` (ticks of 10 ns: the store
+    // drains, flag store to poll match, poll match to the stage part's neighbour columns in registers, the whole kernel -- the
+    // rest of the phases is the difference) and its phase count
     if (wg == (int)(gridDim.x / 2) && threadIdx.x == 0) {
         A.out[8] = (double)nbs.ck_drain; A.out[9] = (double)nbs.ck_wait;
         A.out[10] = (double)((long long)__builtin_amdgcn_s_memrealtime() - ck_begin); A.out[11] = (double)nbs.phase;
+        A.out[12] = (double)late.ck_fetch;
     }
 #endif
     if (wg == 0 && threadIdx.x == 0) {
@@ -400,3 +443,5 @@ finish:
 #undef FZ_YOLD
 #undef FZ_Z
 #undef FZ_ZN
+#undef FZ_U
+#undef FZ_UN

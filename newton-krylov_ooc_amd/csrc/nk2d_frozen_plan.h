@@ -24,6 +24,10 @@
 // of 512 before, one of them spilled) nor the LDS of a compute unit with two workgroups hold it
 // (profiles/r09_frozen_own_state_resources.log).  The kernel and frozen_lds_shape() read this one macro.
 #define NK2D_FROZEN_OWN(E, KIND, TEAM, LEAN) ((E) >= 5 && (E) <= 7 && ((KIND) == 0 || (KIND) == 2) && !(TEAM) && !(LEAN))
+// ... and of those the ones whose waves may exchange stage values with their neighbours (option "frozen_stage_exchange"): all but the
+// piece flavour of the linear-source kind at seven levels per lane, where the body with the exchange beside the others makes the
+// compiler report a spilled register (<7, 0, 0, 1, 0>: that class stays on the body without it)
+#define NK2D_FROZEN_XCHG(E, KIND, TEAM, PIECES, LEAN) (NK2D_FROZEN_OWN(E, KIND, TEAM, LEAN) && !((E) == 7 && (KIND) == 0 && (PIECES)))
 
 // what of a context (nk2d_ctx) and its options the cache's arithmetic reads
 struct FrozenPlanIn {

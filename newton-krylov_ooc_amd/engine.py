@@ -237,6 +237,9 @@ class ModuleEngine:
         # the one-launch frozen year's norm partials out of the way of the hand-over between workgroups (csrc/nk2d_frozen_body.inc)
         if "NK2D_FROZEN_EARLY" in os.environ:
             self.set_option("frozen_early", float(os.environ["NK2D_FROZEN_EARLY"]))
+        # the one-launch frozen year's neighbours exchange stage values instead of Z and Y (csrc/nk2d_frozen_body.inc)
+        if "NK2D_FROZEN_STAGE_EXCHANGE" in os.environ:
+            self.set_option("frozen_stage_exchange", float(os.environ["NK2D_FROZEN_STAGE_EXCHANGE"]))
         # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_TWO_ENDED" in os.environ:
             self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
