@@ -283,7 +283,8 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    preconditioner (option "pc_two_ended"): "pc_setup_rounds" (dependent inversion rounds of the last block elimination: ny,
    or ny / 2 + 1 from both ends), "pc_sub_launches" (dependent mat-vec launches of the last block substitution: 2 ny - 1,
    or at most ny + 2); (option "pc_pivot_wave") "pc_pivot_wave_steps" (panel steps of the last block elimination that ran
-   a one-wave pivot inversion: 0, or ceil(m / 32) * "pc_setup_rounds"). */
+   a one-wave pivot inversion: 0, or ceil(m / 32) * "pc_setup_rounds"); (option "pc_panel") "pc_panel_steps" (64-wide panel
+   steps of the last block elimination: 0 with the option at 32, ceil(m / 64) * "pc_setup_rounds" at 64). */
 int nk2d_get_counter(nk2d_ctx* ctx, const char* name, int64_t* out);
 /* hash of everything a recorded schedule depends on besides the state: grid, module description, tolerances, the
    controller options (jac_fresh, jac_stage, lin_tol, min_sweeps, growth_cap, factor storage), the library version and a
@@ -506,7 +507,15 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    "pc_pivot_wave" (0, default, or 1; opt-in: the 32 x 32 pivot blocks of the preconditioner's Gauss-Jordan inversions are
    inverted by ONE wave in registers -- no LDS round trip and no barrier per pivot -- instead of by four waves through LDS:
    the same operations in the same order, the same bits.  Read at every set-up as "pc_two_ended" is; composes with
-   "pc_fused", "pc_valu", "pc_two_ended" and "pc_fp32".  Counter "pc_pivot_wave_steps") */
+   "pc_fused", "pc_valu", "pc_two_ended" and "pc_fp32".  Counter "pc_pivot_wave_steps"),
+   "pc_panel" (32, default, or 64; any other value is refused and the value stays.  Opt-in: the preconditioner's Gauss-Jordan
+   inversions advance by panels of 64 pivots -- one launch per panel step at every block size, the matrix streamed once per
+   64 pivots, a rank-64 update on the matrix cores, the 64 x 64 pivot blocks inverted by four waves in LDS one pivot after
+   the other -- instead of 32.  The same pivots in the same order, other rounding between them: held to the references of
+   the 32-wide path at its bars, not to its bits.  Read at every set-up as "pc_two_ended" is; "pc_fused" is not consulted;
+   composes with "pc_two_ended" and "pc_fp32"; with "pc_valu" 1 or "pc_pivot_wave" 1 the set-up is refused.  The layout of
+   the stored inverses is that of 32: a factorisation made with 64 is applied whatever the value is by then.  Counter
+   "pc_panel_steps") */
 int nk2d_set_option(nk2d_ctx* ctx, const char* name, double value);
 
 /* block until every operation queued on the context's stream has finished */

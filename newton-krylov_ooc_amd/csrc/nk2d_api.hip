@@ -186,6 +186,12 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
         c->pc_pivot_wave = (int)value;
         return 0;
     }
+    if (key == "pc_panel") {
+        // pivots per panel step of the preconditioner's Gauss-Jordan inversions (nk2d_precond.hip); taken at the next set-up
+        if (value != 32.0 && value != 64.0) return nk2d_fail(c, "nk2d_set_option: pc_panel is 32 or 64");
+        c->pc_panel = (int)value;
+        return 0;
+    }
     if (key == "final_fuse") { c->final_fuse = value != 0.0; return 0; }
     if (key == "year_fences") { c->year_fences = value != 0.0; return 0; }
     if (key == "frozen_persistent") { c->frozen_persistent = value != 0.0; return 0; }
@@ -779,6 +785,8 @@ extern "C" int nk2d_create(const nk2d_desc* desc, nk2d_ctx** out) {
     c->pc_setup_rounds = c->pc_sub_launches = 0;
     c->pc_pivot_wave = 0;
     c->pc_pivot_wave_steps = 0;
+    c->pc_panel = 32;
+    c->pc_panel_steps = 0;
     c->st = nk2d_stats();
     c->prof_every = 0;
     c->snap_ready = 0;
@@ -1176,6 +1184,7 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "pc_setup_rounds") v = c->pc_setup_rounds;
     else if (key == "pc_sub_launches") v = c->pc_sub_launches;
     else if (key == "pc_pivot_wave_steps") v = c->pc_pivot_wave_steps;
+    else if (key == "pc_panel_steps") v = c->pc_panel_steps;
     else if (key == "tape_years_run") v = c->tape_years_run;
     else if (key == "tape_builds") v = c->tape_builds;
     else if (key == "tape_timeouts") v = c->tape_timeouts;

@@ -228,6 +228,8 @@ struct nk2d_ctx {
     int64_t pc_setup_rounds, pc_sub_launches;   // counters (nk2d_get_counter): dependent inversion rounds of the last elimination, dependent mat-vec launches of the last substitution
     int pc_pivot_wave;  // option "pc_pivot_wave": 0 (default) the 32 x 32 pivot blocks of the Gauss-Jordan inversions are inverted by four waves through LDS, 1 by one wave in registers -- the same bits (read at every set-up)
     int64_t pc_pivot_wave_steps;   // counter: panel steps of the last elimination that ran a wave flavour
+    int pc_panel;  // option "pc_panel": 32 (default) or 64 pivots per panel step of the Gauss-Jordan inversions; 64 is the one-launch step k_pc_gj_step64 at every size, pc_fused is not consulted (read at every set-up)
+    int64_t pc_panel_steps;   // counter: 64-wide panel steps of the last elimination
 
     // optional dense-output sampling of the running comp_fcn (history files)
     int hist_n, hist_next;

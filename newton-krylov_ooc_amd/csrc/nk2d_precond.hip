@@ -51,7 +51,7 @@ struct Precond {
     // Gauss-Jordan work buffers below and PREV then hold both chains of a round: twice the systems
     int two_ended, jm;
     double* BUF;   // Gauss-Jordan ping-pong [2][tc][m][m]
-    double* PINV;  // inverses of this and the next panel step's pivot block [2][tc][32][32] (k_pc_gj_step)
+    double* PINV;  // inverses of this and the next panel step's pivot block: [2][tc][32][32] (k_pc_gj_step) or [2][tc][64][64] (k_pc_gj_step64), sized for the latter
     double* ROWS;  // scaled pivot rows    [tc][NB][m]
     double* YV;    // forward-sweep vectors [tc][nb][m]
     double* XV;    // solution vectors      [tc][nb][m]
@@ -728,6 +728,230 @@ __global__ void __launch_bounds__(256) k_pc_gj_step(int m, int p0, int nb, const
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Panel steps of 64 pivots (option "pc_panel" 64): the algorithm of k_pc_gj_step with the panel P = [p0, p0 + nb), nb <= 64
+// and p0 a multiple of 64 -- the m x m matrix goes through the chip once per 64 pivots instead of once per 32, and the
+// update is rank 64, 16 k-steps of v_mfma_f64_16x16x4_f64 per 16 x 16 tile instead of 8.
+//   Pinv = inverse of src[P, P] without pivoting, one pivot after the other as in pc_invert_block, identity beyond nb
+//   R    = Pinv src[P, :]   with the pivot columns replaced by Pinv
+//   dst[i, c] = (c in P ? 0 : src[i, c]) - src[i, P] R[:, c]   for i outside P,   dst[P, :] = R
+// A workgroup owns a 64 x 64 tile of the result, a wave a 32 x 32 quadrant of it.  LDS: two 64 x 65 arrays, 66 560 bytes of
+// dynamic shared memory, two workgroups to a compute unit -- first Pinv and src[P, c], the operands of R; once every wave has
+// its quadrant of R in the accumulators, src[i, P] (requested with everything else, held in registers) takes the place of
+// Pinv and R that of src[P, c] (arrays of their own would be 133 120 bytes and one workgroup to a compute unit).  With
+// 64-aligned panels the next pivot block is the whole tile (p1 / 64, p1 / 64): its workgroup, the launch's first, takes its
+// result through the first array into the registers of its four waves, inverts it there (pc_invert_block64) and leaves the
+// inverse in pinv_out.  PINV holds 64 x 64 per system and parity here.
+// ---------------------------------------------------------------------------------
+#define PC_NB64 64
+#define PC_LDS64_DOUBLES (2 * PC_NB64 * (PC_NB64 + 1))
+
+// The 64 x 64 pivot block by four waves, one pivot after the other (the arithmetic of pc_invert_block): a thread owns column cc
+// of rows r0 + 4 q (r0: its wave, q = 0 .. 15) in registers.  Per pivot pp the column factors a[r][pp] of a wave's rows are
+// in lane pp of that wave (v_readlane, no LDS); the pivot row a[pp][.] belongs to ONE wave, which leaves it in `rowbuf`
+// ([2][64], alternating: one barrier per pivot) at the end of the pivot before.  (A first form kept the whole block in an LDS
+// ping-pong as pc_invert_block does -- 16 broadcast reads and 16 writes per thread and pivot: 1.0 us per pivot, 65 us per
+// block, the whole launch)
+__device__ __forceinline__ void pc_invert_block64(double (*rowbuf)[PC_NB64], double (&mine)[PC_NB64 / 4], int r0, int cc, int nb) {
+    const int w = __builtin_amdgcn_readfirstlane(r0);
+    if (w == 0) rowbuf[0][cc] = mine[0];
+    __syncthreads();
+    // unrolled: static register indices (row pp is entry pp / 4 of wave pp % 4), under the workgroup-uniform guard pp < nb
+#pragma unroll
+    for (int pp = 0; pp < PC_NB64; ++pp) {
+        if (pp < nb) {
+            const double* row = rowbuf[pp & 1];
+            const double piv = 1.0 / row[pp];
+            const double prow = ((cc == pp) ? 1.0 : row[cc]) * piv;
+            // the column factors, taken before anything of this pivot is written; then "(cc == pp) ? 0.0 : old" as a move
+            // under the lane mask of column pp (pc_invert_block_wave)
+            double f[PC_NB64 / 4];
+#pragma unroll
+            for (int q = 0; q < PC_NB64 / 4; ++q) f[q] = pc_wave_lane(mine[q], pp);
+            if (cc == pp) {
+#pragma unroll
+                for (int q = 0; q < PC_NB64 / 4; ++q) mine[q] = 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < PC_NB64 / 4; ++q) mine[q] = __builtin_fma(-f[q], prow, mine[q]);
+            if (w == (pp & 3)) mine[pp >> 2] = prow;
+            if (pp + 1 < nb && w == ((pp + 1) & 3)) rowbuf[(pp + 1) & 1][cc] = mine[((pp + 1) >> 2) & 15];
+            __syncthreads();
+        }
+    }
+}
+
+// inverse of the FIRST 64-wide pivot block of every system: pinv [nsys][64][64], identity beyond nb
+__global__ void __launch_bounds__(256) k_pc_pivot_invert64(int m, int p0, int nb, const double* __restrict__ src,
+                                                           double* __restrict__ pinv) {
+    __shared__ double rowbuf[2][PC_NB64];
+    const int tr = blockIdx.z;
+    const size_t base = (size_t)tr * m * m;
+    const int r0 = threadIdx.x >> 6, cc = threadIdx.x & 63;
+    double mine[PC_NB64 / 4];
+#pragma unroll
+    for (int q = 0; q < PC_NB64 / 4; ++q) {
+        const int r = r0 + 4 * q;
+        mine[q] = (r < nb && cc < nb) ? src[base + (size_t)(p0 + r) * m + (p0 + cc)] : ((r == cc) ? 1.0 : 0.0);
+    }
+    pc_invert_block64(rowbuf, mine, r0, cc, nb);
+#pragma unroll
+    for (int q = 0; q < PC_NB64 / 4; ++q) pinv[((size_t)tr * PC_NB64 + r0 + 4 * q) * PC_NB64 + cc] = mine[q];
+}
+
+__global__ void __launch_bounds__(256) k_pc_gj_step64(int m, int p0, int nb, const double* __restrict__ src, double* __restrict__ dst,
+                                                      const double* __restrict__ pinv_in, double* __restrict__ pinv_out) {
+    extern __shared__ double pc_lds64[];
+    double (*sf)[PC_NB64 + 1] = reinterpret_cast<double (*)[PC_NB64 + 1]>(pc_lds64);                               // src[i, P]
+    double (*sr)[PC_NB64 + 1] = reinterpret_cast<double (*)[PC_NB64 + 1]>(pc_lds64 + PC_NB64 * (PC_NB64 + 1));     // src[P, c], then R[:, c]
+    double (*rowbuf)[PC_NB64] = reinterpret_cast<double (*)[PC_NB64]>(pc_lds64 + PC_NB64 * (PC_NB64 + 1));        // (its workgroup only)
+    const int tr = blockIdx.z;
+    const size_t base = (size_t)tr * m * m;
+    // the next pivot block: rows / columns p1 .. p1 + nb1 of the result, the tile (tn, tn); its workgroup runs first
+    const int p1 = p0 + PC_NB64;
+    const bool has_next = p1 < m;
+    const int nb1 = has_next ? min(PC_NB64, m - p1) : 0;
+    const int tn = p1 / 64;
+    int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    if (has_next) {
+        if (bx == 0 && by == 0) { bx = tn; by = tn; }
+        else if (bx == tn && by == tn) { bx = 0; by = 0; }
+    }
+    const bool owns_next = has_next && bx == tn && by == tn;
+    const int i0 = by * 64, c0 = bx * 64;
+    const int tid = threadIdx.x;
+    const int wv = tid >> 6, l = tid & 63;
+    const int ib = (wv >> 1) * 32, jb = (wv & 1) * 32;
+    const int lr16 = l >> 4, lc16 = l & 15;
+    // ---- every request first: the operands, then the tile itself
+    double lf[16], lrw[16], tile[2][2][4];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int i = i0 + wv + 4 * k;
+        lf[k] = (i < m && l < nb) ? src[base + (size_t)i * m + p0 + l] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int q = wv + 4 * k, c = c0 + l;
+        lrw[k] = (c < m && q < nb) ? src[base + (size_t)(p0 + q) * m + c] : 0.0;
+    }
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int i = i0 + ib + 16 * ti + lr16 + 4 * reg, c = c0 + jb + 16 * tj + lc16;
+                tile[ti][tj][reg] = (i < m && c < m) ? src[base + (size_t)i * m + c] : 0.0;
+            }
+    // (Pinv: 32 KB per system, out of L2)
+    double lpin[16];
+    {
+        const double* __restrict__ pin = pinv_in + (size_t)tr * PC_NB64 * PC_NB64;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) lpin[k] = pin[(wv + 4 * k) * PC_NB64 + l];
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        sf[wv + 4 * k][l] = lpin[k];      // Pinv first; src[i, P] waits in registers
+        sr[wv + 4 * k][l] = lrw[k];
+    }
+    __syncthreads();
+    // ---- this tile's piece of the scaled pivot rows on the matrix cores too: R = Pinv src[P, c0 .. c0 + 64), a wave its 32 x 32
+    // quadrant, the pivot columns replaced by Pinv.  (Every tile of a column of tiles computes the same R: with 64 pivots that is
+    // as much arithmetic as the update itself.  A first form did it as k_pc_gj_step does, 1024 multiply-adds per thread with
+    // the rows of Pinv as scalar operands -- 8 KB per wave through the scalar cache: DESIGN.md section 4.)  R stays in the
+    // accumulators until every wave has read Pinv and the raw rows, then takes the raw rows' place, and src[i, P] that of Pinv
+    {
+        pc_v4d accr[2][2];
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int tj = 0; tj < 2; ++tj) accr[ti][tj] = (pc_v4d){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int ks = 0; ks < PC_NB64 / 4; ++ks) {
+            const int k = 4 * ks + lr16;      // raw rows beyond nb were staged as zeros
+            const double a0 = sf[ib + lc16][k], a1 = sf[ib + 16 + lc16][k];
+            const double b0 = sr[k][jb + lc16], b1 = sr[k][jb + 16 + lc16];
+            accr[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, accr[0][0], 0, 0, 0);
+            accr[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, accr[0][1], 0, 0, 0);
+            accr[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, accr[1][0], 0, 0, 0);
+            accr[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, accr[1][1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int pr = ib + 16 * ti + lr16 + 4 * reg, cl = jb + 16 * tj + lc16;
+                    const int c = c0 + cl;
+                    if (c >= p0 && c < p0 + nb) accr[ti][tj][reg] = sf[pr][c - p0];
+                    if (pr >= nb) accr[ti][tj][reg] = 0.0;
+                }
+        __syncthreads();
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) sr[ib + 16 * ti + lr16 + 4 * reg][jb + 16 * tj + lc16] = accr[ti][tj][reg];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) sf[wv + 4 * k][l] = lf[k];
+    }
+    __syncthreads();
+    // ---- the rank-nb update: 16 k-steps of four pivots
+    pc_v4d acc[2][2];
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = (pc_v4d){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ks = 0; ks < PC_NB64 / 4; ++ks) {
+        const int k = 4 * ks + lr16;      // pivots beyond nb were staged as zeros
+        const double a0 = sf[ib + lc16][k], a1 = sf[ib + 16 + lc16][k];
+        const double b0 = sr[k][jb + lc16], b1 = sr[k][jb + 16 + lc16];
+        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    // (the workgroup whose tile is the next pivot block keeps what it stores -- where src[i, P] was staged, once every wave
+    // has read it; its rows lie outside P, so it reads nothing of R from here on)
+    if (owns_next) __syncthreads();
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int il = ib + 16 * ti + lr16 + 4 * reg, cl = jb + 16 * tj + lc16;
+                const int i = i0 + il, c = c0 + cl;
+                double val = (il == cl) ? 1.0 : 0.0;        // (beyond the matrix: the identity the pivot block is padded with)
+                if (i < m && c < m) {
+                    if (i >= p0 && i < p0 + nb) {
+                        val = sr[i - p0][cl];
+                    } else {
+                        const bool pivot_col = c >= p0 && c < p0 + nb;
+                        val = (pivot_col ? 0.0 : tile[ti][tj][reg]) - acc[ti][tj][reg];
+                    }
+                    dst[base + (size_t)i * m + c] = val;
+                }
+                if (owns_next) sf[il][cl] = val;
+            }
+    if (!owns_next) return;
+    // ---- the next step's pivot block, inverted here by the four waves: through LDS once, from the layout of the matrix
+    // cores into that of pc_invert_block64; the pivot rows then change hands where R was
+    __syncthreads();
+    const int r0 = wv, cc = l;
+    double mine[PC_NB64 / 4];
+#pragma unroll
+    for (int q = 0; q < PC_NB64 / 4; ++q) mine[q] = sf[r0 + 4 * q][cc];
+    pc_invert_block64(rowbuf, mine, r0, cc, nb1);
+#pragma unroll
+    for (int q = 0; q < PC_NB64 / 4; ++q) pinv_out[((size_t)tr * PC_NB64 + r0 + 4 * q) * PC_NB64 + cc] = mine[q];
+}
+
 // Dense mat-vec of the block substitution for even m: 16-byte loads, the whole row of a wave requested at once
 // (up to 10 x 1 KB per wave in flight), the vector staged once per workgroup in LDS instead of being re-read
 // through L1 by every wave.  Same epilogues as k_pc_gemv below.
@@ -1192,6 +1416,17 @@ int precond_build(nk2d_ctx* c, int mode, int nt, int nslot, int nsys, const doub
     const int want_ends = c->pc_two_ended ? 1 : 0;
     if (want_ends && c->pc_valu)
         return nk2d_fail(c, "preconditioner set-up: pc_two_ended 1 has no round-1 kernels (pc_valu 1); set one of the two to 0");
+    // (option "pc_panel": read here and in pc_gj_invert, at every set-up; the 64-wide panel step exists as one launch on the
+    // matrix cores with the four-wave inversion only)
+    if (c->pc_panel == 64 && c->pc_valu)
+        return nk2d_fail(c, "preconditioner set-up: pc_panel 64 has no round-1 kernels (pc_valu 1); set pc_panel to 32 or pc_valu to 0");
+    if (c->pc_panel == 64 && c->pc_pivot_wave)
+        return nk2d_fail(c, "preconditioner set-up: pc_panel 64 has no one-wave pivot inversion (pc_pivot_wave 1); set pc_panel to 32 or pc_pivot_wave to 0");
+    if (c->pc_panel == 64) {
+        // 66 560 bytes of dynamic shared memory: above the 64 KB a kernel gets without asking
+        const int lds = (int)(sizeof(double) * PC_LDS64_DOUBLES);
+        NK2D_CHECK(c, hipFuncSetAttribute((const void*)k_pc_gj_step64, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
     const bool reuse = pc && pc->mode == mode && pc->nt == nt && pc->m == m && pc->nb == c->ny && pc->cap_sys >= nsys &&
                        pc->fp32 == want32 && pc->two_ended == want_ends;
     if (!reuse) {
@@ -1229,7 +1464,7 @@ int precond_build(nk2d_ctx* c, int mode, int nt, int nslot, int nsys, const doub
             NK2D_CHECK(c, hipMalloc((void**)&pc->SINV, sizeof(double) * cap * pc->nb * mm));
         }
         NK2D_CHECK(c, hipMalloc((void**)&pc->BUF, sizeof(double) * 2 * gj * mm));
-        NK2D_CHECK(c, hipMalloc((void**)&pc->PINV, sizeof(double) * 2 * gj * PC_NB * PC_NB));
+        NK2D_CHECK(c, hipMalloc((void**)&pc->PINV, sizeof(double) * 2 * gj * PC_NB64 * PC_NB64));
         NK2D_CHECK(c, hipMalloc((void**)&pc->ROWS, sizeof(double) * gj * PC_NB * pc->m));
         NK2D_CHECK(c, hipMalloc((void**)&pc->YV, sizeof(double) * cap * pc->nb * pc->m));
         NK2D_CHECK(c, hipMalloc((void**)&pc->XV, sizeof(double) * cap * pc->nb * pc->m));
@@ -1251,6 +1486,25 @@ int pc_gj_invert(nk2d_ctx* c, Precond* pc, int nsys) {
     const size_t mm = (size_t)pc->m * pc->m;
     const int m = pc->m;
     int src = 0;
+    if (c->pc_panel == 64) {
+        // (option "pc_panel" 64: ceil(m / 64) one-launch steps at every size, pc_fused is not consulted; the first pivot
+        // block's inverse by a launch of its own, the others by the step before)
+        const size_t lds = sizeof(double) * PC_LDS64_DOUBLES;
+        const dim3 grd((m + 63) / 64, (m + 63) / 64, nsys);
+        for (int p0 = 0; p0 < m; p0 += PC_NB64) {
+            const int nbk = std::min(PC_NB64, m - p0);
+            c->pc_panel_steps += 1;
+            const double* from = pc->BUF + (size_t)src * nsys * mm;
+            double* to = pc->BUF + (size_t)(1 - src) * nsys * mm;
+            double* pin = pc->PINV + (size_t)((p0 / PC_NB64) & 1) * nsys * PC_NB64 * PC_NB64;
+            double* pout = pc->PINV + (size_t)(1 - ((p0 / PC_NB64) & 1)) * nsys * PC_NB64 * PC_NB64;
+            if (p0 == 0)
+                hipLaunchKernelGGL(k_pc_pivot_invert64, dim3(1, 1, nsys), dim3(256), 0, nk2d_s(c), m, 0, nbk, from, pin);
+            hipLaunchKernelGGL(k_pc_gj_step64, grd, dim3(256), lds, nk2d_s(c), m, p0, nbk, from, to, (const double*)pin, pout);
+            src = 1 - src;
+        }
+        return src;
+    }
     // (option "pc_pivot_wave": read here, at every round of a set-up; the wave flavours compute the bits of the others.
     // Measured at m = 1248: k_pc_pivot_invert 13.2 -> 12.7 us, k_pc_gj_rows 16.7 -> 15.0 us, k_pc_gj_step 29.6 -> 29.9 us --
     // the fused step had the inversion hidden already: profiles/r13_pc_pivot_wave.log)
@@ -1329,7 +1583,7 @@ int precond_eliminate_ends(nk2d_ctx* c) {
     auto above = [&](int j) -> const double* {
         return (j >= nb - 1) ? nullptr : pc->fp32 ? pc->PREV + (size_t)nsys * mm : pc->SINV + (size_t)(j + 1) * mm;
     };
-    c->pc_setup_rounds = c->pc_pivot_wave_steps = 0;
+    c->pc_setup_rounds = c->pc_pivot_wave_steps = c->pc_panel_steps = 0;
     for (int s = 0; s <= jm; ++s) {
         const int jl = s, jr = nb - 1 - s;
         const bool meet = s == jm, pair = !meet && jr > jm;
@@ -1359,7 +1613,7 @@ int precond_eliminate(nk2d_ctx* c) {
     PcDev D = make_pcdev(c, pc);
     const int m = pc->m;
     const dim3 blk(256), grd((m + 255) / 256, m, nsys);
-    c->pc_setup_rounds = c->pc_pivot_wave_steps = 0;
+    c->pc_setup_rounds = c->pc_pivot_wave_steps = c->pc_panel_steps = 0;
     for (int j = 0; j < pc->nb; ++j) {
         // the Schur inverse of the column before: inside SINV ([nsys][nb][m][m]), or -- single precision storage -- the
         // double precision copy kept of that one column ([nsys][m][m])

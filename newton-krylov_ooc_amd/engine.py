@@ -246,6 +246,9 @@ class ModuleEngine:
         # pivot blocks of the preconditioner's Gauss-Jordan inversions by one wave in registers (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_PIVOT_WAVE" in os.environ:
             self.set_option("pc_pivot_wave", float(os.environ["NK2D_PC_PIVOT_WAVE"]))
+        # pivots per panel step of the preconditioner's Gauss-Jordan inversions, 32 or 64 (csrc/nk2d_precond.hip), read at its set-up
+        if "NK2D_PC_PANEL" in os.environ:
+            self.set_option("pc_panel", float(os.environ["NK2D_PC_PANEL"]))
         self.set_option("jac_fresh", float(os.environ.get("NK2D_JAC_FRESH", DEFAULT_JAC_FRESH)))
         self.set_option("growth_cap", float(os.environ.get("NK2D_GROWTH_CAP", DEFAULT_GROWTH_CAP)))
         self.set_option("jac_stage", float(os.environ.get("NK2D_JAC_STAGE", DEFAULT_JAC_STAGE)))
