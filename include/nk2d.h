@@ -32,6 +32,10 @@
  *   nk2d_shift_factor/solve         sp_linalg.spsolve(mat - shift * mat_id, .) and the solves inside
  *                                   sp_linalg.eigs of phosphorus.apply_precond_jacobian,
  *                                   py_driver_2d/phosphorus.py:233-255
+ *   nk2d_precond_setup_states on a phosphorus context (the null vector): the rest of
+ *                                   phosphorus.apply_precond_jacobian per vector (extrapolation to zero shift, projection
+ *                                   along the null vector), phosphorus.py:257-274: with it nk2d_precond_apply is the
+ *                                   phosphorus preconditioner in one call
  *   nk2d_dot                        TracerModuleStateBase.dot_prod (weighted region mean),
  *                                   nk_ooc/tracer_module_state_base.py:379-388
  *   nk2d_axpby / nk2d_scale / nk2d_diff_scale
@@ -284,7 +288,9 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    or ny / 2 + 1 from both ends), "pc_sub_launches" (dependent mat-vec launches of the last block substitution: 2 ny - 1,
    or at most ny + 2); (option "pc_pivot_wave") "pc_pivot_wave_steps" (panel steps of the last block elimination that ran
    a one-wave pivot inversion: 0, or ceil(m / 32) * "pc_setup_rounds"); (option "pc_panel") "pc_panel_steps" (64-wide panel
-   steps of the last block elimination: 0 with the option at 32, ceil(m / 64) * "pc_setup_rounds" at 64). */
+   steps of the last block elimination: 0 with the option at 32, ceil(m / 64) * "pc_setup_rounds" at 64);
+   "pc_phos_applies" (nk2d_precond_apply calls of this context that ran the one-call phosphorus preconditioner,
+   the null-vector form of nk2d_precond_setup_states). */
 int nk2d_get_counter(nk2d_ctx* ctx, const char* name, int64_t* out);
 /* hash of everything a recorded schedule depends on besides the state: grid, module description, tolerances, the
    controller options (jac_fresh, jac_stage, lin_tol, min_sweeps, growth_cap, factor storage), the library version and a
@@ -307,8 +313,30 @@ int nk2d_comp_fcn_hist(nk2d_ctx* ctx, nk2d_vec x, nk2d_vec fx, nk2d_stats* stats
 int nk2d_precond_setup(nk2d_ctx* ctx);
 /* the same for a forced module whose Jacobian depends on the state (file source with sink_thres):
    states[i] = the tracer at the end of the i-th third of [t0, t1], as forced.apply_precond_jacobian
-   reads it from the preconditioner file (py_driver_2d/forced.py:222-236) */
+   reads it from the preconditioner file (py_driver_2d/forced.py:222-236).
+   On a phosphorus context (module_kind 1) the call takes ONE vector, states[0] = e_hat, and completes the set-up of the
+   extrapolated phosphorus preconditioner of phosphorus.py:197-274 (the null-vector form; no entry point of its own, the ABI
+   keeps its 56): it declares that systems 0 and 1 of the current nk2d_shift_factor factorisation are that preconditioner --
+   shifts[0] = shift, shifts[1] = shift / 2 with shift = half the second smallest eigenvalue of mat = scale J -- and e_hat
+   the null vector of mat scaled to unit region mean (e / <e, 1>); the context keeps a copy.  From then on
+   nk2d_precond_apply and nk2d_gmres_solve work on this context.  Refused when there is no shifted factorisation or it has
+   fewer than two systems, and when states or states[0] is null; on a context that is neither a forced module with forcing
+   files nor phosphorus the call is refused as before.  Any later nk2d_shift_factor on the context removes the declaration,
+   as would any other set-up (the storage is shared; e_hat belongs to one factorisation).  The eigen-pair itself stays above
+   this boundary, where the reference has it (sp_linalg.eigs): a binding factorises mat - mu I with nk2d_shift_factor and
+   hands nk2d_shift_solve to eigs as OPinv (shift-invert), as PhosphorusPrecond does with its own Arnoldi loop. */
 int nk2d_precond_setup_states(nk2d_ctx* ctx, const nk2d_vec* states);
+/* nk2d_precond_apply: out = M^-1 v with the preconditioner of the last set-up.  On a phosphorus context (module_kind 1) that
+   is the extrapolated preconditioner declared by the null-vector form of nk2d_precond_setup_states above, the whole of
+   phosphorus.apply_precond_jacobian's per-vector work (phosphorus.py:257-274) in one call: v goes into the right-hand sides
+   of both shifted systems in one launch, both run down ONE block substitution chain (2 ny - 1 dependent mat-vec launches,
+   at most ny + 2 with "pc_two_ended", instead of that many per system; "pc_fp32" / "pc_refine" as in nk2d_shift_solve),
+   then  s = 2 A_1^-1 v - A_0^-1 v,  out = s - <s, 1> e_hat - v  region by region; nothing is read back and the host does
+   not wait.  out may be v.  The result is, bit for bit, that of the five calls nk2d_shift_solve(0), nk2d_shift_solve(1),
+   nk2d_axpby(2, half, -1, full), nk2d_axpby(1, s, -nk2d_dot(s, ones), e_hat), nk2d_axpby(1, ., -1, v).  Without the
+   declaration a phosphorus context is refused.  Counter "pc_phos_applies": the calls of this context that took this
+   path; "pc_sub_launches" is then the one chain of the call.  (PhosphorusPrecond of the Python layer uses the call with
+   NK2D_PHOS_PC_FUSED=1 in the environment, read when the engine is created; default 0: the five calls.) */
 int nk2d_precond_apply(nk2d_ctx* ctx, nk2d_vec v, nk2d_vec out);
 /* shifted systems of the phosphorus preconditioner (phosphorus.py:233-255): factorise
    A_i = scale * J(t, lin_state) - shifts[i] * I (all tracers of the module coupled, nshift <=
@@ -378,8 +406,8 @@ int nk2d_jvp(nk2d_ctx* ctx, nk2d_vec x, nk2d_vec fx, nk2d_vec v, nk2d_vec w, nk2
    iteration >= min_iter and || sum_j c_j w_j + M^-1 fx || < rel_tol * beta in every region, or at
    max_iter.  Everything stays in HBM; nothing is written to disk (the Python mirror of KrylovSolver
    keeps the reference's file trail).  The preconditioner is nk2d_precond_apply: call
-   nk2d_precond_setup (or _setup_states) first; the phosphorus module, whose preconditioner is
-   assembled above this boundary, is refused.
+   nk2d_precond_setup (or _setup_states) first; on a phosphorus context nk2d_shift_factor with the two shifts and
+   nk2d_precond_setup_states with the null vector -- without that declaration the phosphorus module is refused before any device work.
    Outputs (caller-owned host buffers, zero padded): beta [nreg]; h_mat [max_iter+1][max_iter][nreg]
    (the reference's h_mat[module] with the iteration axes first); resid_norm [max_iter][nreg];
    coeff [max_iter][nreg] of the last iteration; *iters = iterations done; increment = the device

@@ -783,6 +783,7 @@ extern "C" int nk2d_create(const nk2d_desc* desc, nk2d_ctx** out) {
     c->pc_refine = 1;
     c->pc_two_ended = 0;
     c->pc_setup_rounds = c->pc_sub_launches = 0;
+    c->pc_phos_applies = 0;
     c->pc_pivot_wave = 0;
     c->pc_pivot_wave_steps = 0;
     c->pc_panel = 32;
@@ -1185,6 +1186,7 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "pc_sub_launches") v = c->pc_sub_launches;
     else if (key == "pc_pivot_wave_steps") v = c->pc_pivot_wave_steps;
     else if (key == "pc_panel_steps") v = c->pc_panel_steps;
+    else if (key == "pc_phos_applies") v = c->pc_phos_applies;
     else if (key == "tape_years_run") v = c->tape_years_run;
     else if (key == "tape_builds") v = c->tape_builds;
     else if (key == "tape_timeouts") v = c->tape_timeouts;

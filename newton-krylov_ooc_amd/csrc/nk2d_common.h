@@ -230,6 +230,7 @@ struct nk2d_ctx {
     int64_t pc_pivot_wave_steps;   // counter: panel steps of the last elimination that ran a wave flavour
     int pc_panel;  // option "pc_panel": 32 (default) or 64 pivots per panel step of the Gauss-Jordan inversions; 64 is the one-launch step k_pc_gj_step64 at every size, pc_fused is not consulted (read at every set-up)
     int64_t pc_panel_steps;   // counter: 64-wide panel steps of the last elimination
+    int64_t pc_phos_applies;  // counter: nk2d_precond_apply calls of this context that ran the one-call phosphorus preconditioner (null-vector form of nk2d_precond_setup_states)
 
     // optional dense-output sampling of the running comp_fcn (history files)
     int hist_n, hist_next;
@@ -724,3 +725,5 @@ int nk2d_radau_year(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, nk2d_stats* stats, con
                     int64_t replay_n, double* record, int64_t record_cap, int64_t* record_n, bool replay_own = false);
 // nk2d_precond.hip
 void nk2d_precond_free(nk2d_ctx* c);
+// the current factorisation is the extrapolated phosphorus preconditioner (nk2d_precond_setup_states with the null vector since the last factorisation)
+bool nk2d_precond_has_nullspace(const nk2d_ctx* c);

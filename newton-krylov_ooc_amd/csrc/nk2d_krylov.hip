@@ -234,9 +234,11 @@ extern "C" int nk2d_gmres_solve(nk2d_ctx* c, nk2d_vec x, nk2d_vec fx, double rel
     NK2D_CHECK(c, hipSetDevice(c->dev));
     if (!x || !fx || !increment) return nk2d_fail(c, "nk2d_gmres_solve: null vector");
     if (max_iter < 1 || max_iter > 256) return nk2d_fail(c, "nk2d_gmres_solve: 1 <= max_iter <= 256");
-    if (c->kind == 1)
-        return nk2d_fail(c, "nk2d_gmres_solve: the phosphorus preconditioner is assembled above the C ABI "
-                            "(phosphorus.py); use the KrylovSolver mirror");
+    // (before any device work: a phosphorus context's preconditioner is nk2d_precond_apply only once its two shifted systems
+    // are factorised and declared)
+    if (c->kind == 1 && !nk2d_precond_has_nullspace(c))
+        return nk2d_fail(c, "nk2d_gmres_solve: the phosphorus preconditioner is not installed: call nk2d_shift_factor with the "
+                            "two shifts {shift, shift / 2}, then nk2d_precond_setup_states with the null vector (or use the KrylovSolver mirror)");
     const int nreg = c->nreg, ld = max_iter;
     if (iters) *iters = 0;
     std::vector<double> beta(nreg), rbeta(nreg), one(nreg, 1.0);

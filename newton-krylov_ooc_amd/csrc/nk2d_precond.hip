@@ -56,6 +56,11 @@ struct Precond {
     double* YV;    // forward-sweep vectors [tc][nb][m]
     double* XV;    // solution vectors      [tc][nb][m]
     double dt;
+    // nk2d_precond_setup_states on a phosphorus context: systems 0 and 1 of this mode 1 factorisation are the extrapolated phosphorus preconditioner;
+    // every set-up takes the declaration away again (precond_build), the two packed vectors stay with the allocation
+    int nullspace;
+    double* EHAT;  // the caller's null-space vector, scaled to unit region mean (a copy)
+    double* PS;    // 2 half - full of the apply under way
 };
 
 // planes index
@@ -1373,6 +1378,103 @@ __global__ void k_pc_result_all(int ncol, int ny, int nz, int m, const double* _
     store_col<E>(out, task, lane, vv);
 }
 
+// ---------------------------------------------------------------------------------
+// The extrapolated phosphorus preconditioner in one call (precond_set_nullspace; phosphorus.py:257-274 of the reference):
+// what PhosphorusPrecond.apply composes of two nk2d_shift_solve, three nk2d_axpby and one nk2d_dot, on the two systems side
+// by side and without a read-back.  The arithmetic is that of k_pc_rhs_all, k_pc_result_all, k_axpby and k_dot, operation for
+// operation (products first, then the sum; a broadcast coefficient is 1.0 where the mask is <= 0): the same bits.
+// ---------------------------------------------------------------------------------
+// a coefficient that is the same in every region, broadcast as k_axpby broadcasts it
+__device__ __forceinline__ double pc_bcast1(double coef, int m) { return (m > 0) ? coef : 1.0; }
+
+// k_pc_rhs_all for both systems: v into blocks of system 0 and system 1 of rhs (and of keep, where the residual needs them)
+template <int E>
+__global__ void k_pc_phos_rhs(int ncol, int ny, int nz, int m, size_t vstride, const double* __restrict__ v,
+                              double* __restrict__ rhs, double* __restrict__ keep) {
+    const int lane = threadIdx.x & 63;
+    const int task = blockIdx.x * NK2D_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (task >= ncol) return;
+    const int tr = task / ny, j = task - tr * ny;
+    double vv[E];
+    load_col<E>(v, task, lane, vv);
+    const size_t at = (size_t)j * m + (size_t)tr * nz;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int k = lane * E + e;
+        if (k < nz) {
+            rhs[at + k] = vv[e];
+            rhs[vstride + at + k] = vv[e];
+            if (keep) {
+                keep[at + k] = vv[e];
+                keep[vstride + at + k] = vv[e];
+            }
+        }
+    }
+}
+
+// s = 2.0 * half + (-1.0) * full from the solutions of system 1 (half) and system 0 (full) in x, stored packed, and the
+// partials of dot(s, ones) as k_dot leaves them: part[task * nreg + r - 1] = sum over the column's cells of region r of
+// wn * (s * 1.0)
+template <int E>
+__global__ void k_pc_phos_combine(int ncol, int ny, int nz, int m, int nreg, size_t vstride, const double* __restrict__ x,
+                                  const double* __restrict__ wn, const int32_t* __restrict__ mask, double* __restrict__ s,
+                                  double* __restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int task = blockIdx.x * NK2D_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (task >= ncol) return;
+    const int tr = task / ny, j = task - tr * ny;
+    const double* full = x + (size_t)j * m + (size_t)tr * nz;
+    const double* half = full + vstride;
+    double ss[E], ww[E];
+    int mm[E];
+    load_col<E>(wn, j, lane, ww);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int k = lane * E + e;
+        const double fu = (k < nz) ? full[k] : 0.0;     // (the padding as k_pc_result_all leaves it)
+        const double ha = (k < nz) ? half[k] : 0.0;
+        mm[e] = mask[(size_t)j * (E * 64) + e * 64 + lane];
+        ss[e] = pc_bcast1(2.0, mm[e]) * ha + pc_bcast1(-1.0, mm[e]) * fu;
+    }
+    store_col<E>(s, task, lane, ss);
+#pragma unroll
+    for (int e = 0; e < E; ++e) ss[e] = ww[e] * (ss[e] * 1.0);
+    for (int r = 1; r <= nreg; ++r) {
+        double acc = 0.0;
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (mm[e] == r) { acc += ss[e]; any = true; }
+        double tot = 0.0;
+        if (__any(any)) tot = wave_sum(acc);
+        if (lane == 0) part[(size_t)task * nreg + (r - 1)] = tot;
+    }
+}
+
+// out = 1.0 * (1.0 * s + bcast(-d) * e_hat) + bcast(-1.0) * v with the region sums d of dot(s, ones) read from device
+// memory; out may be v (every cell is read and written by its own thread)
+template <int E>
+__global__ void k_pc_phos_finish(int ncol, int ny, const double* __restrict__ s, const double* __restrict__ d,
+                                 const double* __restrict__ e_hat, const double* v, const int32_t* __restrict__ mask,
+                                 double* out) {
+    const int lane = threadIdx.x & 63;
+    const int task = blockIdx.x * NK2D_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (task >= ncol) return;
+    const int j = task % ny;
+    double ss[E], ee[E], vv[E];
+    load_col<E>(s, task, lane, ss);
+    load_col<E>(e_hat, task, lane, ee);
+    load_col<E>(v, task, lane, vv);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int m = mask[(size_t)j * (E * 64) + e * 64 + lane];
+        const double nd = (m > 0) ? -d[m - 1] : 1.0;
+        const double t = pc_bcast1(1.0, m) * ss[e] + nd * ee[e];
+        vv[e] = pc_bcast1(1.0, m) * t + pc_bcast1(-1.0, m) * vv[e];
+    }
+    store_col<E>(out, task, lane, vv);
+}
+
 PcDev make_pcdev(const nk2d_ctx* c, const Precond* pc) {
     PcDev P;
     P.m = pc->m; P.nb = pc->nb; P.nz = c->nz; P.ny = c->ny; P.nt = pc->nt; P.tc = c->tc;
@@ -1391,7 +1493,7 @@ PcDev make_pcdev(const nk2d_ctx* c, const Precond* pc) {
 void nk2d_precond_free(nk2d_ctx* c) {
     Precond* pc = (Precond*)c->precond;
     if (!pc) return;
-    double* bufs[] = {pc->PJ, pc->SINV, pc->BUF, pc->YV, pc->XV, pc->ROWS, pc->PREV, pc->RV, pc->X0, pc->PINV};
+    double* bufs[] = {pc->PJ, pc->SINV, pc->BUF, pc->YV, pc->XV, pc->ROWS, pc->PREV, pc->RV, pc->X0, pc->PINV, pc->EHAT, pc->PS};
     for (double* b : bufs)
         if (b) (void)hipFree(b);
     if (pc->SINV32) (void)hipFree(pc->SINV32);
@@ -1406,6 +1508,9 @@ namespace {
 // ylin: linearisation state of every time level (state dependent modules), or null
 int precond_build(nk2d_ctx* c, int mode, int nt, int nslot, int nsys, const double* times, const double* const* ylin) {
     Precond* pc = (Precond*)c->precond;
+    // (a set-up of any kind takes the declaration of precond_set_nullspace away: the storage is shared, and its e_hat
+    // belongs to the factorisation it was declared for)
+    if (pc) pc->nullspace = 0;
     const int m = nslot * c->nz;
     // gigabytes of Schur inverses: keep the allocation when the next factorisation fits in it (the
     // phosphorus preconditioner factorises three shifted systems per Newton iteration)
@@ -1435,6 +1540,8 @@ int precond_build(nk2d_ctx* c, int mode, int nt, int nslot, int nsys, const doub
         c->precond = pc;
         pc->PJ = pc->SINV = pc->BUF = pc->YV = pc->XV = pc->ROWS = pc->PREV = pc->RV = pc->X0 = pc->PINV = nullptr;
         pc->SINV32 = nullptr;
+        pc->EHAT = pc->PS = nullptr;
+        pc->nullspace = 0;
         pc->fp32 = want32;
         pc->two_ended = want_ends;
         pc->cap_sys = std::max(nsys, mode == 1 ? 2 : nsys);
@@ -1761,6 +1868,7 @@ int precond_substitute(nk2d_ctx* c, int sys0, int nsys) {
 }  // namespace
 
 static int precond_setup_levels(nk2d_ctx* c, const double* const* states);
+static int precond_set_nullspace(nk2d_ctx* c, nk2d_vec e_hat);
 
 extern "C" int nk2d_precond_setup(nk2d_ctx* c) {
     NK2D_CHECK(c, hipSetDevice(c->dev));
@@ -1774,7 +1882,12 @@ extern "C" int nk2d_precond_setup(nk2d_ctx* c) {
 // forced.py:222-236); they enter through the sink threshold only
 extern "C" int nk2d_precond_setup_states(nk2d_ctx* c, const nk2d_vec* states) {
     NK2D_CHECK(c, hipSetDevice(c->dev));
-    if (c->kind != 2) return nk2d_fail(c, "nk2d_precond_setup_states: forced modules with forcing files only");
+    // (a phosphorus context: ONE vector, the scaled null vector of the extrapolated preconditioner -- a declaration on top of
+    // the current shifted factorisation, not a set-up of its own)
+    if (c->kind == 1) return precond_set_nullspace(c, states ? states[0] : nullptr);
+    if (c->kind != 2)
+        return nk2d_fail(c, "nk2d_precond_setup_states: forced modules with forcing files only (and phosphorus contexts, "
+                            "module_kind 1: the null vector)");
     if (!states || !states[0] || !states[1] || !states[2]) return nk2d_fail(c, "nk2d_precond_setup_states: three states needed");
     const double* lv[3] = {(const double*)states[0], (const double*)states[1], (const double*)states[2]};
     return precond_setup_levels(c, lv);
@@ -1837,9 +1950,67 @@ extern "C" int nk2d_shift_solve(nk2d_ctx* c, int32_t i, nk2d_vec v, nk2d_vec out
     return 0;
 }
 
+bool nk2d_precond_has_nullspace(const nk2d_ctx* c) {
+    const Precond* pc = (const Precond*)c->precond;
+    return pc && pc->mode == 1 && pc->nsys >= 2 && pc->nullspace;
+}
+
+// nk2d_precond_setup_states on a phosphorus context (states[0] = e_hat): the declaration
+static int precond_set_nullspace(nk2d_ctx* c, nk2d_vec e_hat) {
+    Precond* pc = (Precond*)c->precond;
+    if (!pc || pc->mode != 1 || pc->nsys < 2)
+        return nk2d_fail(c, "nk2d_precond_setup_states (phosphorus, the null vector): call nk2d_shift_factor with the two shifts "
+                            "{shift, shift / 2} first");
+    if (!e_hat) return nk2d_fail(c, "nk2d_precond_setup_states (phosphorus, the null vector): null vector");
+    if (!pc->EHAT) NK2D_CHECK(c, hipMalloc((void**)&pc->EHAT, sizeof(double) * c->nv));
+    if (!pc->PS) NK2D_CHECK(c, hipMalloc((void**)&pc->PS, sizeof(double) * c->nv));
+    NK2D_CHECK(c, hipMemcpyAsync(pc->EHAT, e_hat, sizeof(double) * c->nv, hipMemcpyDeviceToDevice, nk2d_s(c)));
+    pc->nullspace = 1;
+    return 0;
+}
+
+// M^-1 v of the phosphorus module: both shifted systems down ONE substitution chain, the extrapolation to zero shift, the
+// projection along the null vector and "- v", queued on the stream without a synchronisation or a read-back
+static int precond_apply_phos(nk2d_ctx* c, const double* v, double* out) {
+    Precond* pc = (Precond*)c->precond;
+    const int m = pc->m;
+    const size_t vstride = (size_t)pc->nb * m;
+    NK2D_DISPATCH_E(c->E, hipLaunchKernelGGL(k_pc_phos_rhs<EE>, dim3(nk2d_grid(c->ncol)), dim3(NK2D_BLOCK), 0, nk2d_s(c),
+                                              c->ncol, c->ny, c->nz, m, vstride, v, pc->XV, pc->fp32 ? pc->RV : (double*)nullptr));
+    NK2D_TRY(precond_substitute(c, 0, 2));
+    if (pc->fp32) {
+        // single precision inverses: the "pc_refine" corrections of nk2d_shift_solve, for both systems at once
+        const size_t nvec = 2 * vstride;
+        PcDev D = make_pcdev(c, pc);
+        for (int it = 0; it < c->pc_refine; ++it) {
+            NK2D_CHECK(c, hipMemcpyAsync(pc->X0, pc->XV, sizeof(double) * nvec, hipMemcpyDeviceToDevice, nk2d_s(c)));
+            for (int sys = 0; sys < 2; ++sys)
+                hipLaunchKernelGGL(k_pc_residual_shift, dim3((m + 255) / 256, pc->nb, 1), dim3(256), 0, nk2d_s(c), D, sys,
+                                   pc->RV + (size_t)sys * vstride, pc->X0 + (size_t)sys * vstride, pc->XV + (size_t)sys * vstride);
+            NK2D_TRY(precond_substitute(c, 0, 2));
+            hipLaunchKernelGGL(k_pc_add, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, nk2d_s(c), pc->XV, pc->X0, nvec);
+        }
+    }
+    NK2D_DISPATCH_E(c->E, hipLaunchKernelGGL(k_pc_phos_combine<EE>, dim3(nk2d_grid(c->ncol)), dim3(NK2D_BLOCK), 0, nk2d_s(c),
+                                              c->ncol, c->ny, c->nz, m, c->nreg, vstride, pc->XV, c->WN, c->MASK, pc->PS, c->PART));
+    NK2D_CHECK(c, hipGetLastError());
+    NK2D_TRY(nk2d_k_reduce(c, c->ncol, c->nreg, nullptr));      // the region sums stay in RED
+    NK2D_DISPATCH_E(c->E, hipLaunchKernelGGL(k_pc_phos_finish<EE>, dim3(nk2d_grid(c->ncol)), dim3(NK2D_BLOCK), 0, nk2d_s(c),
+                                              c->ncol, c->ny, pc->PS, c->RED, pc->EHAT, v, c->MASK, out));
+    NK2D_CHECK(c, hipGetLastError());
+    c->pc_phos_applies++;
+    return 0;
+}
+
 extern "C" int nk2d_precond_apply(nk2d_ctx* c, nk2d_vec v, nk2d_vec out) {
     NK2D_CHECK(c, hipSetDevice(c->dev));
     Precond* pc = (Precond*)c->precond;
+    if (c->kind == 1) {
+        if (!nk2d_precond_has_nullspace(c))
+            return nk2d_fail(c, "nk2d_precond_apply: call nk2d_precond_setup first (a phosphorus context: nk2d_shift_factor with "
+                                "the two shifts {shift, shift / 2}, then nk2d_precond_setup_states with the null vector)");
+        return precond_apply_phos(c, (const double*)v, (double*)out);
+    }
     if (!pc || pc->mode != 0) return nk2d_fail(c, "nk2d_precond_apply: call nk2d_precond_setup first");
     const int m = pc->m;
     // right-hand sides into XV (used as r_j), forward sweep writes YV

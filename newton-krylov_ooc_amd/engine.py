@@ -44,6 +44,11 @@ DEFAULT_GROWTH_CAP = 0.0
 # (0: launch by launch; 1: free-running years; 3: frozen years too).
 
 
+def phos_pc_fused_from_env():
+    """NK2D_PHOS_PC_FUSED in the environment: 1 = PhosphorusPrecond.apply is one nk2d_precond_apply; default 0, the five calls"""
+    return int(os.environ.get("NK2D_PHOS_PC_FUSED", "0")) != 0
+
+
 class Nk2dError(RuntimeError):
     pass
 
@@ -203,6 +208,10 @@ class ModuleEngine:
         self._handle = ctx
         self.device_ctl = 0
         self._precond_ready = False
+        self._nullspace_declared = False
+        # the phosphorus preconditioner's apply as ONE nk2d_precond_apply (precond_set_nullspace) instead of five calls: the
+        # same bits, half the dependent launches (phosphorus.py); read here, used by PhosphorusPrecond
+        self.phos_pc_fused = phos_pc_fused_from_env()
         if "NK2D_STREAM_YEARS" in os.environ:
             self.set_option("stream_years", float(os.environ["NK2D_STREAM_YEARS"]))
         if "NK2D_FROZEN_TAPE" in os.environ:
@@ -600,6 +609,7 @@ class ModuleEngine:
 
     # ---- preconditioner -----------------------------------------------------------
     def precond_setup(self):
+        self._nullspace_declared = False
         self._chk(self._lib.nk2d_precond_setup(self._ctx))
         self._precond_ready = True
 
@@ -607,14 +617,27 @@ class ModuleEngine:
         """preconditioner of a forced module whose Jacobian depends on the state: `states` = the
         tracer (device vectors) at the end of each third of the year (forced.py:222-236)"""
         ptrs = (ctypes.c_void_p * 3)(*[v.ptr for v in states])
+        self._nullspace_declared = False
         self._chk(self._lib.nk2d_precond_setup_states(self._ctx, ptrs))
         self._precond_ready = True
 
     def shift_factor(self, t, scale, shifts):
         """factorise scale * J(t, lin_state) - shift * I for every shift (block elimination)"""
         arr = np.ascontiguousarray(shifts, dtype=np.float64)
+        self._nullspace_declared = False
         self._chk(self._lib.nk2d_shift_factor(self._ctx, float(t), float(scale), len(arr), _dp(arr)))
         self._precond_ready = False
+
+    def precond_set_nullspace(self, e_hat):
+        """declare systems 0 and 1 of the current shift_factor factorisation (shifts {s, s / 2}) the extrapolated phosphorus
+        preconditioner, with `e_hat` the null vector scaled to unit region mean: precond_apply is then one
+        nk2d_precond_apply and gmres_solve accepts this engine, until the next set-up of any kind"""
+        if self.module_kind != 1:
+            raise Nk2dError("precond_set_nullspace: phosphorus engines (module_kind 1) only")
+        # (the null-vector form of nk2d_precond_setup_states: one vector on a phosphorus context)
+        ptrs = (ctypes.c_void_p * 1)(None if e_hat is None else e_hat.ptr)
+        self._chk(self._lib.nk2d_precond_setup_states(self._ctx, ptrs))
+        self._nullspace_declared = True
 
     def shift_solve(self, i, v, out=None):
         out = self.new_vec() if out is None else out
@@ -637,11 +660,13 @@ class ModuleEngine:
         return self._state_precond
 
     def precond_apply(self, v, out=None):
-        if self.module_kind == 1:
+        if self.module_kind == 1 and not self._nullspace_declared:
             if getattr(self, "_state_precond", None) is None:
                 raise Nk2dError("phosphorus preconditioner: call precond_setup_state(po4) first")
-            return self._state_precond.apply(v, out=out)
-        if not self._precond_ready:
+            if not self._state_precond.fused:
+                return self._state_precond.apply(v, out=out)
+            # (a one-call preconditioner whose factorisation was replaced since: the library refuses and says what to call)
+        if self.module_kind != 1 and not self._precond_ready:
             self.precond_setup()
         out = self.new_vec() if out is None else out
         self._chk(self._lib.nk2d_precond_apply(self._ctx, v.ptr, out.ptr))

@@ -13,8 +13,10 @@ iterate's history, `T` = one year) the reference computes, for every application
 Here the two shifted matrices are factorised ONCE per preconditioner (block elimination over
 the ypos columns with the three tracers of a column in one block, `nk2d_shift_factor`) and every
 application is two block substitutions (`nk2d_shift_solve`) plus region-weighted algebra, all on
-the device.  The eigen-pair comes from shift-invert Arnoldi with the same block solver at a
-small POSITIVE shift, where `-(mat - mu I)` is a non-singular M-matrix.
+the device -- five calls, or with `NK2D_PHOS_PC_FUSED=1` ONE `nk2d_precond_apply` that sends both
+systems down one substitution chain (`nk2d_precond_setup_states` with the null vector; the same
+bits).  The eigen-pair comes from shift-invert Arnoldi with the same block solver at a small
+POSITIVE shift, where `-(mat - mu I)` is a non-singular M-matrix.
 
 The reference's `sigma=0.0` asks ARPACK to invert the exactly singular `mat`; its second
 eigenvalue then depends on ARPACK's random start vector (real part scattered by several per
@@ -50,6 +52,10 @@ class PhosphorusPrecond:
         eng.shift_factor(self.t_mid, self.scale, [self.shift, 0.5 * self.shift])
         e_vect = eng.upload(null_vect.reshape(eng.shape))
         self.e_hat = eng.scale(e_vect, 1.0 / eng.dot(e_vect, self.ones))
+        # NK2D_PHOS_PC_FUSED=1 (read when the engine was created): the library keeps e_hat and an apply is ONE call
+        self.fused = bool(getattr(eng, "phos_pc_fused", False))
+        if self.fused:
+            eng.precond_set_nullspace(self.e_hat)
         logging.getLogger(__name__).info(
             "phosphorus preconditioner: %d Arnoldi solves (factor %.2f s, solves + orthogonalisation %.2f s, host %.2f s), "
             "shift %.6e, factorisation of the two shifted systems %.2f s",
@@ -127,6 +133,10 @@ class PhosphorusPrecond:
 
     def apply(self, v, out=None):
         eng = self.eng
+        if self.fused:
+            # both shifted systems down one substitution chain, no read-back: the bits of the five calls below (a
+            # factorisation replaced since is refused by the library)
+            return eng.precond_apply(v, out=out)
         sol_full = eng.shift_solve(0, v)
         sol_half = eng.shift_solve(1, v)
         sol = eng.axpby(2.0, sol_half, -1.0, sol_full, out=sol_half)
