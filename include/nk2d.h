@@ -273,6 +273,7 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    "frozen_early_bits" (option "frozen_early" as in effect in that year: 0 wherever "frozen_lds_bits" lacks 16 and 32),
    "frozen_stage_exchange_bits" (option "frozen_stage_exchange" as in effect in that year, under the same rule -- and 0 whatever the
    option says for linear sources at seven levels per lane on a cache in pieces, whose kernel has no body for it),
+   "frozen_xlane_bits" (option "frozen_xlane" as in effect in that year: 0 wherever "frozen_stage_exchange_bits" is 0),
    "frozen_step_sums_hash" (64-bit FNV-1a hash of the bits of the step sums the last whole-year check of a frozen year read: the
    norm sums of every step's last Newton iteration and of the one before -- the same for the same year by whatever path),
    "frozen_forced_years" (one-launch years only option "frozen_forced" made possible; also counted in "frozen_persistent_years",
@@ -518,6 +519,16 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    addition, on the producing side: the same bits; Z goes to memory only in the rows with an error estimate and in the last;
    not on a cache in pieces with linear sources at seven levels per lane, which stays on the body without it;
    counter "frozen_stage_exchange_bits"),
+   "frozen_xlane" (1 or 0: on top of the stage-value exchange, the Newton phase moves values between lanes -- the vertical stencil
+   of the tendencies, the parallel cyclic reduction of the two tridiagonal solves, the sum of the norm partial -- with DPP and
+   v_permlane swaps in the VALU instead of ds_bpermute through LDS; every lane receives the same 64 bits: the same year bit for
+   bit; no decision, not part of the schedule fingerprint; counter "frozen_xlane_bits"),
+   "xlane_selftest_in0" .. "xlane_selftest_in63" and "xlane_selftest_run" (the self-test of those moves, no entry point of its own:
+   the 64 doubles of one wave, lane by lane, then 1 to run it: one wave moves them -- as a complex value too: that vector and
+   the same vector read backwards -- by 1, 2, 4, 8, 16 and 32 lanes; counter "xlane_selftest_<w>_<row>_<lane>" is then the 64 bits
+   lane <lane> holds of row <row>, as __shfl_up / __shfl_down give them (w = 0) and as the VALU helper gives them (w = 1); rows
+   0-5 up, 6-11 down, 12-17 / 18-23 complex up (re / im), 24-29 / 30-35 complex down, 36 the sum over the wave, of which only
+   lane 0 holds the total),
    "frozen_sums_poison" (0, default, or 1; for tests: the rows of norm partials are filled with NaN before every frozen year, so
    that a partial the year does not store fails its check instead of passing on what an earlier year left there),
    "frozen_by_column" (1,

@@ -248,14 +248,15 @@ __device__ __forceinline__ void load_coef_lds(const double* s, int lane, ColCoef
 
 // c: own column, cs / cn: columns j-1 / j+1 (any finite values at the walls, their
 // face coefficients are zero), kv: vertical mixing coeff between level k and k+1
-template <int E, int KIND = 0>
+// (XL: the helper family of the vertical stencil's cross-lane moves, nk2d_common.h)
+template <int E, int KIND = 0, int XL = 0>
 __device__ __forceinline__ void tend_col(const DevP& P, const ColCoef<E>& cf, const double (&c)[E],
                                          const double (&cs)[E], const double (&cn)[E], const double (&kv)[E],
                                          int tr, int lane, double (&out)[E]) {
     double cprev[E], cnext[E], kvprev[E];
-    shift_prev<E>(c, cprev, lane, 0.0);
-    shift_next<E>(c, cnext, lane, 0.0);
-    shift_prev<E>(kv, kvprev, lane, 0.0);
+    shift_prev<E, XL>(c, cprev, lane, 0.0);
+    shift_next<E, XL>(c, cnext, lane, 0.0);
+    shift_prev<E, XL>(kv, kvprev, lane, 0.0);
     const double surf = P.surf[tr], starget = P.starget[tr], decay = P.decay[tr];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -894,6 +895,8 @@ __device__ __forceinline__ void w_lds_put(double* s, int r, int lane, const doub
 //                stage part of the next (OwnState::z)
 //   bit 7  norm : the update part may form the norm partial behind its stores and leave it to the caller to store (LateNorm)
 //   bit 8  xchg : the neighbours exchange stage values U_i = Y + Z_i instead of Z_i and Y (StageXchg; on top of bits 4 and 5)
+//   bit 9  xlane: the cross-lane moves of the vertical stencil, of the two solves and of the norm partial go through the VALU
+//                 (the xl_ helpers of nk2d_common.h, option "frozen_xlane" of the one-launch year; only on top of CL 447)
 struct LdsSrc {
     const double* coef;
     double* w;
@@ -944,7 +947,7 @@ struct StageXchg {
     int keep_z;         // the update part stores Z too
 };
 // sum over the wave of the squared scaled increments (radau.py:113-129): the expressions of the update part of newton_fused_body
-template <int E>
+template <int E, int XL = 0>
 __device__ __forceinline__ double norm_partial_sum(const DevP& P, const double (&yy)[E], const double (&d0v)[E],
                                                    const double (&d1v)[E], const double (&d2v)[E]) {
     double acc = 0.0;
@@ -954,7 +957,8 @@ __device__ __forceinline__ double norm_partial_sum(const DevP& P, const double (
         const double d0 = d0v[e] / sc, d1 = d1v[e] / sc, d2 = d2v[e] / sc;
         acc += (d0 * d0 + d1 * d1) + d2 * d2;
     }
-    return wave_sum(acc);
+    if constexpr ((XL & NK2D_XL_SUM) != 0) return xl_wave_sum(acc);
+    else return wave_sum(acc);
 }
 
 template <int E, int KIND, int FACTOR, int STAGE, int MP = 0, int FINAL = 0, int CL = 0>
@@ -963,6 +967,8 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
                                                   OwnState<E>* own = nullptr, LateNorm* late = nullptr,
                                                   const StageXchg* xc = nullptr) {
     static_assert(!(CL & 256) || (CL & 48) == 48, "the stage-value exchange needs the column's whole own state");
+    static_assert(!(CL & 512) || (CL & 511) == 447, "the VALU cross-lane moves exist on top of the stage-value exchange only");
+    constexpr int XL = (CL & 512) ? NK2D_FROZEN_XLANE_MOVES : 0;
     const double* coef_lds = (CL & 1) ? lds->coef : nullptr;
     double* w_lds = (CL & 2) ? lds->w : nullptr;
     (void)coef_lds; (void)w_lds;
@@ -1038,7 +1044,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
 #pragma unroll
             for (int e = 0; e < E; ++e) { c[e] = y0[e] + c[e]; cs[e] = ys[e] + cs[e]; cn[e] = yn[e] + cn[e]; }
             }
-            tend_col<E, KIND>(P, cf, c, cs, cn, kv, tr, lane, f);
+            tend_col<E, KIND, XL>(P, cf, c, cs, cn, kv, tr, lane, f);
             if constexpr (KIND == 2) forced_sources<E>(P, A.st.kv[i], j, lane, c, f);
             if constexpr (KIND == 1) {
                 double u1[E], u2[E], v1[E], v2[E];
@@ -1143,7 +1149,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         }
 #pragma unroll
         for (int e = 0; e < E; ++e) fr[e] = ((lane * E + e) < P.nz) ? fr[e] : 0.0;
-        tridiag_apply<E, double>(a, cc, inv, tab, fr, lane);
+        tridiag_apply<E, double, XL>(a, cc, inv, tab, fr, lane);
     }
     // complex system
     {
@@ -1194,7 +1200,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
             const bool valid = (lane * E + e) < P.nz;
             r[e] = c_make(valid ? fcr[e] : 0.0, valid ? fci[e] : 0.0);
         }
-        tridiag_apply<E, cplx>(a, cc, inv, tab, r, lane);
+        tridiag_apply<E, cplx, XL>(a, cc, inv, tab, r, lane);
 #pragma unroll
         for (int e = 0; e < E; ++e) { fcr[e] = r[e].re; fci[e] = r[e].im; }
     }
@@ -1251,7 +1257,8 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
             const double d0 = fr[e] / sc, d1 = fcr[e] / sc, d2 = fci[e] / sc;
             acc += (d0 * d0 + d1 * d1) + d2 * d2;
         }
-        acc = wave_sum(acc);
+        if constexpr ((XL & NK2D_XL_SUM) != 0) acc = xl_wave_sum(acc);
+        else acc = wave_sum(acc);
         if (lane == 0) st_mp<MP>(A.part + task, acc);
     }
 #pragma unroll
@@ -1320,7 +1327,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         }
         if constexpr ((CL & 48) != 0) own->valid = 1;
         if constexpr (CL & 128) {
-            if (norm_late) { late->acc = norm_partial_sum<E>(P, yy, fr, fcr, fci); late->part = A.part + task; late->pending = 1; }
+            if (norm_late) { late->acc = norm_partial_sum<E, XL>(P, yy, fr, fcr, fci); late->part = A.part + task; late->pending = 1; }
         }
         return;
     }
@@ -1357,7 +1364,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
     }
     if constexpr ((CL & 48) != 0) own->valid = 1;
     if constexpr (CL & 128) {
-        if (norm_late) { late->acc = norm_partial_sum<E>(P, yy, fr, fcr, fci); late->part = A.part + task; late->pending = 1; }
+        if (norm_late) { late->acc = norm_partial_sum<E, XL>(P, yy, fr, fcr, fci); late->part = A.part + task; late->pending = 1; }
     }
 }
 
@@ -2496,6 +2503,8 @@ struct FrozenArgs {
                                  // U and UN, [3][nv] doubles each, lie behind the synchronisation block `arrive` points to (yr_xchg_offset():
                                  // no field of their own either)
 #define NK2D_FROZEN_XCHG_OF(coef_lds) (((coef_lds) >> 9) & 1)
+                                 // Bit 10: option "frozen_xlane", set only where bit 9 is (NK2D_FROZEN_XLANE: the instantiations with the body)
+#define NK2D_FROZEN_XLANE_OF(coef_lds) (((coef_lds) >> 10) & 1)
     int by_column;               // 1: a workgroup is ONE ypos column with all its tracers (a wave each) instead of adjacent columns of one tracer
     // option "frozen_forced" bit 2 (forced module with a thresholded sink, lean cache): the rows' file-source planes at their Jacobian
     // times, [n][np] behind J in the slab (a cache in pieces: PieceTab::oS), and 1 where the year forms UPR from them

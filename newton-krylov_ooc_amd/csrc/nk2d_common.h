@@ -36,6 +36,12 @@
 #define NK2D_FROZEN_EARLY_DEFAULT 1
 // option "frozen_stage_exchange" as a context starts with it (1: the neighbours of the one-launch year exchange stage values, not Z and Y)
 #define NK2D_FROZEN_STAGE_EXCHANGE_DEFAULT 1
+// option "frozen_xlane" as a context starts with it (1: the cross-lane moves of the one-launch year's Newton phase go through the VALU)
+#define NK2D_FROZEN_XLANE_DEFAULT 1
+// ... and which moves that body takes from the xl_ helpers: the sum of the distances (1 | 2 | 4 | 8 | 16 | 32) and NK2D_XL_SUM (64)
+#ifndef NK2D_FROZEN_XLANE_MOVES
+#define NK2D_FROZEN_XLANE_MOVES 97
+#endif
 struct nk2d_ctx {
     nk2d_desc d;
     int nz, ny, tc, E, nzp, ncol, nreg;
@@ -149,6 +155,8 @@ struct nk2d_ctx {
     int frozen_early_bits; // counter "frozen_early_bits": the option in effect in the one-launch year launched last
     int frozen_stage_exchange;      // option "frozen_stage_exchange": the neighbours of the one-launch year exchange the stage values Y + Z_i, not Z_i and Y
     int frozen_stage_exchange_bits; // counter "frozen_stage_exchange_bits": the option in effect in the one-launch year launched last
+    int frozen_xlane;               // option "frozen_xlane": the Newton phase of the one-launch year moves values between lanes in the VALU, not through LDS
+    int frozen_xlane_bits;          // counter "frozen_xlane_bits": the option in effect in the one-launch year launched last
     int frozen_by_column; // option "frozen_by_column": a workgroup of the one-launch year is one ypos column with all its tracers
     int frozen_alloc_async;   // option "frozen_alloc_async": a schedule cache above 8 GB is allocated by a thread of its own
     int frozen_cache_after;   // option "frozen_cache_after": frozen years of a schedule that run launch by launch before its cache is built (default 0; -1: 0 for a cache below 8 GB, 3 above)
@@ -466,18 +474,127 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// ---------------------------------------------------------------------------------
+// The same moves in the VALU (option "frozen_xlane" of the one-launch year).  __shfl_up / __shfl_down with a constant distance
+// compile to one ds_bpermute_b32 per 32-bit half plus the VALU that forms its lane index: LDS-pipeline instructions that return
+// in order behind the wave's own LDS reads and share the compute unit's one LDS pipeline.  gfx950 moves lanes in the VALU too:
+// DPP on v_mov_b32 (wave_shr:1 / wave_shl:1 across the wave; row_shr / row_shl / row_ror inside a row of 16 lanes, with row and
+// bank masks that leave `old` in the lanes they disable) and v_permlane16_swap / v_permlane32_swap.  No lane index, no lgkmcnt.
+// Builtins only: the compiler inserts the wait states these reads need behind a VALU write.
+// Contract: xl_up<S>(v) / xl_down<S>(v) hold in EVERY lane the 64 bits __shfl_up(v, S, 64) / __shfl_down(v, S, 64) hold there --
+// the lane's own value where it has no partner (the PCR multiplies that slot by a zero: another value there could turn the
+// sign of a zero or make a NaN).  S is 1, 2, 4, 8, 16 or 32.
+//   S = 1      wave_shr:1 / wave_shl:1, bound_ctrl off, old = the value: 1 move per half
+//   S = 32     permlane32_swap(v, v): its two results are the two directions: 1 move per half for both
+//   S = 16     permlane16_swap(v, v) = rows (0 0 2 2), (1 1 3 3); permlane32_swap of those = rows (0 0 1 1), (2 2 3 3); up is
+//              (0 0 1 2), down is (1 2 3 3): one select each
+//   S = 2,4,8  inside a row row_shr:S / row_shl:S; the S lanes of a row whose partner lies in the row before (after) take it
+//              from the S = 16 move of the value, rotated inside its row (row_ror), under a row mask that leaves out the row
+//              with no partner and a bank mask that covers those lanes -- that DPP writes first and the row shift, which keeps
+//              `old` exactly in the lanes with no source inside the row, second: no select
+// ---------------------------------------------------------------------------------
+#define NK2D_DPP_ROW_SHL(n) (0x100 + (n))
+#define NK2D_DPP_ROW_SHR(n) (0x110 + (n))
+#define NK2D_DPP_ROW_ROR(n) (0x120 + (n))
+#define NK2D_DPP_WAVE_SHL1 0x130
+#define NK2D_DPP_WAVE_SHR1 0x138
+__device__ __forceinline__ int xl_lane() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+// both directions of one 32-bit half (what a direction does not need the compiler drops)
+template <int S>
+__device__ __forceinline__ void xl_both32(int x, int& up, int& dn) {
+    static_assert(S == 1 || S == 2 || S == 4 || S == 8 || S == 16 || S == 32, "distance of a cross-lane move");
+    if constexpr (S == 1) {
+        up = __builtin_amdgcn_update_dpp(x, x, NK2D_DPP_WAVE_SHR1, 0xF, 0xF, false);
+        dn = __builtin_amdgcn_update_dpp(x, x, NK2D_DPP_WAVE_SHL1, 0xF, 0xF, false);
+    } else if constexpr (S == 32) {
+        const auto p = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
+        up = (int)p[0];
+        dn = (int)p[1];
+    } else {
+        const auto p = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);    // rows (0 0 2 2), (1 1 3 3)
+        const auto q = __builtin_amdgcn_permlane32_swap(p[0], p[1], false, false);                  // rows (0 0 1 1), (2 2 3 3)
+        const int row = xl_lane() >> 4;
+        const int u16 = (int)(row == 2 ? q[0] : p[0]);      // rows (0 0 1 2)
+        const int d16 = (int)(row == 1 ? q[1] : p[1]);      // rows (1 2 3 3)
+        if constexpr (S == 16) {
+            up = u16;
+            dn = d16;
+        } else {
+            // (a bank is four lanes: at S = 2 the mask covers two lanes too many, which the row shift then writes)
+            constexpr int lo = S == 8 ? 0x3 : 0x1, hi = S == 8 ? 0xC : 0x8;
+            const int tu = __builtin_amdgcn_update_dpp(x, u16, NK2D_DPP_ROW_ROR(S), 0xE, lo, false);
+            up = __builtin_amdgcn_update_dpp(tu, x, NK2D_DPP_ROW_SHR(S), 0xF, 0xF, false);
+            const int td = __builtin_amdgcn_update_dpp(x, d16, NK2D_DPP_ROW_ROR(16 - S), 0x7, hi, false);
+            dn = __builtin_amdgcn_update_dpp(td, x, NK2D_DPP_ROW_SHL(S), 0xF, 0xF, false);
+        }
+    }
+}
+template <int S>
+__device__ __forceinline__ void xl_both(double v, double& up, double& dn) {
+    int ulo, uhi, dlo, dhi;
+    xl_both32<S>(__double2loint(v), ulo, dlo);
+    xl_both32<S>(__double2hiint(v), uhi, dhi);
+    up = __hiloint2double(uhi, ulo);
+    dn = __hiloint2double(dhi, dlo);
+}
+template <int S>
+__device__ __forceinline__ double xl_up(double v) { double u, d; xl_both<S>(v, u, d); return u; }
+template <int S>
+__device__ __forceinline__ double xl_down(double v) { double u, d; xl_both<S>(v, u, d); return d; }
+template <int S>
+__device__ __forceinline__ cplx xl_up(cplx v) { return c_make(xl_up<S>(v.re), xl_up<S>(v.im)); }
+template <int S>
+__device__ __forceinline__ cplx xl_down(cplx v) { return c_make(xl_down<S>(v.re), xl_down<S>(v.im)); }
+
+// wave_sum's additions in wave_sum's association; the total is valid in lane 0 -- and only there: each level moves only what
+// lane 0's tree reads (lanes 0 .. S-1 take lanes S .. 2S-1), one move per half
+template <int S>
+__device__ __forceinline__ int xl_fold32(int x) {
+    if constexpr (S == 32) return (int)__builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false)[1];
+    else if constexpr (S == 16) return (int)__builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false)[1];
+    else return __builtin_amdgcn_update_dpp(x, x, NK2D_DPP_ROW_SHL(S), 0xF, 0xF, false);
+}
+template <int S>
+__device__ __forceinline__ double xl_fold(double v) {
+    return __hiloint2double(xl_fold32<S>(__double2hiint(v)), xl_fold32<S>(__double2loint(v)));
+}
+__device__ __forceinline__ double xl_wave_sum(double v) {
+    v += xl_fold<32>(v); v += xl_fold<16>(v); v += xl_fold<8>(v);
+    v += xl_fold<4>(v); v += xl_fold<2>(v); v += xl_fold<1>(v);
+    return v;
+}
+
+// The helper family of a body (template parameter XL of tridiag_apply, shift_prev / shift_next, tend_col, norm_partial_sum):
+// 0 is __shfl, today's text; otherwise the sum of the distances S that go through the VALU (1, 2, 4, 8, 16, 32: each is its own
+// bit), the others staying on ds_bpermute, plus NK2D_XL_SUM for xl_wave_sum.
+#define NK2D_XL_SUM 64
+template <int XL, int S, typename T>
+__device__ __forceinline__ T xl_sel_up(T v) {
+    if constexpr ((XL & S) != 0) return xl_up<S>(v);
+    else return shfl_up_t(v, S);
+}
+template <int XL, int S, typename T>
+__device__ __forceinline__ T xl_sel_down(T v) {
+    if constexpr ((XL & S) != 0) return xl_down<S>(v);
+    else return shfl_down_t(v, S);
+}
+
 // value at level k-1 for every level a lane owns (fill at k = 0)
-template <int E>
+template <int E, int XL = 0>
 __device__ __forceinline__ void shift_prev(const double (&a)[E], double (&o)[E], int lane, double fill) {
-    double up = __shfl_up(a[E - 1], 1, 64);
+    double up;
+    if constexpr ((XL & 1) != 0) up = xl_up<1>(a[E - 1]);
+    else up = __shfl_up(a[E - 1], 1, 64);
     o[0] = (lane == 0) ? fill : up;
 #pragma unroll
     for (int e = 1; e < E; ++e) o[e] = a[e - 1];
 }
 // value at level k+1 for every level a lane owns (fill past the last lane)
-template <int E>
+template <int E, int XL = 0>
 __device__ __forceinline__ void shift_next(const double (&a)[E], double (&o)[E], int lane, double fill) {
-    double dn = __shfl_down(a[0], 1, 64);
+    double dn;
+    if constexpr ((XL & 1) != 0) dn = xl_down<1>(a[0]);
+    else dn = __shfl_down(a[0], 1, 64);
     o[E - 1] = (lane == 63) ? fill : dn;
 #pragma unroll
     for (int e = 0; e < E - 1; ++e) o[e] = a[e + 1];
@@ -601,7 +718,25 @@ __device__ __forceinline__ void tridiag_factor(const double (&a)[E], const doubl
     tab[13] = G;
 }
 
-template <int E, typename T>
+// one level of tridiag_apply's parallel cyclic reduction with the helper family XL
+template <int XL, int S, typename T>
+__device__ __forceinline__ T pcr_apply_level(T R, T k1, T k2) {
+    T Rm, Rp;
+    if constexpr ((XL & S) != 0) {
+        if constexpr (sizeof(T) == sizeof(double)) {
+            xl_both<S>(R, Rm, Rp);
+        } else {
+            xl_both<S>(R.re, Rm.re, Rp.re);
+            xl_both<S>(R.im, Rm.im, Rp.im);
+        }
+    } else {
+        Rm = shfl_up_t(R, S);
+        Rp = shfl_down_t(R, S);
+    }
+    return t_nfma(t_nfma(R, Rm, k1), Rp, k2);
+}
+
+template <int E, typename T, int XL = 0>
 __device__ __forceinline__ void tridiag_apply(const double (&a)[E], const double (&c)[E], const T (&inv)[E],
                                               const T (&tab)[NK2D_TAB], T (&r)[E], int lane) {
     T al[E], be[E];
@@ -623,19 +758,28 @@ __device__ __forceinline__ void tridiag_apply(const double (&a)[E], const double
             al[i] = t_nfma(al[i], m, al[i + 1]);
             be[i] = t_neg(t_mul(m, be[i + 1]));
         }
-        T n_r = shfl_down_t(r[0], 1);
+        T n_r = xl_sel_down<XL, 1>(r[0]);
         R = t_nfma(r[E - 1], tab[13], n_r);
     } else {
         R = r[0];
     }
+    if constexpr (XL != 0) {
+        R = pcr_apply_level<XL, 1>(R, tab[0], tab[6]);
+        R = pcr_apply_level<XL, 2>(R, tab[1], tab[7]);
+        R = pcr_apply_level<XL, 4>(R, tab[2], tab[8]);
+        R = pcr_apply_level<XL, 8>(R, tab[3], tab[9]);
+        R = pcr_apply_level<XL, 16>(R, tab[4], tab[10]);
+        R = pcr_apply_level<XL, 32>(R, tab[5], tab[11]);
+    } else {
     int lv = 0;
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1, ++lv) {
         T Rm = shfl_up_t(R, s), Rp = shfl_down_t(R, s);  // multipliers are 0 where no partner
         R = t_nfma(t_nfma(R, Rm, tab[lv]), Rp, tab[6 + lv]);
     }
+    }
     T xl = t_mul(R, tab[12]);
-    T xp = shfl_up_t(xl, 1);
+    T xp = xl_sel_up<XL, 1>(xl);
     if (lane == 0) xp = t_zero(T());
     if constexpr (E >= 2) {
 #pragma unroll

@@ -731,6 +731,11 @@ static int frozen_year_args(nk2d_ctx* c, const nk2d_frozen_cache* fc, const Froz
     c->frozen_stage_exchange_bits =
         ((A.coef_lds & 48) == 48 && NK2D_FROZEN_XCHG(c->E, c->kind, team_year, pl.pieces, pl.lean)) ? c->frozen_stage_exchange : 0;
     A.coef_lds |= c->frozen_stage_exchange_bits << 9;
+    // option "frozen_xlane", bit 10, only on top of bit 9 and in the instantiations that have the body (NK2D_FROZEN_XLANE): no decision,
+    // not part of the schedule fingerprint either
+    c->frozen_xlane_bits =
+        (c->frozen_stage_exchange_bits != 0 && NK2D_FROZEN_XLANE(c->E, c->kind, team_year, pl.pieces, pl.lean)) ? c->frozen_xlane : 0;
+    A.coef_lds |= c->frozen_xlane_bits << 10;
     return 0;
 }
 
@@ -767,9 +772,9 @@ static int frozen_launch_year(nk2d_ctx* c, const FrozenPlan& pl, int64_t n, DevP
     const double* o = c->hYR_OUT;
     if ((int)o[0] != 0 || (int64_t)o[1] != n) return 2;
 #ifdef NK2D_FROZEN_CLOCKS
-    std::fprintf(stderr, "frozen clocks (early %d, stage exchange %d): %.0f phases, per phase drain %.3f us, flag store to poll match %.3f us, "
+    std::fprintf(stderr, "frozen clocks (early %d, stage exchange %d, xlane %d): %.0f phases, per phase drain %.3f us, flag store to poll match %.3f us, "
                  "poll match to neighbours loaded %.3f us, rest %.3f us; kernel %.3f ms\n",
-                 c->frozen_early_bits, c->frozen_stage_exchange_bits, o[11], 0.01 * o[8] / o[11], 0.01 * o[9] / o[11], 0.01 * o[12] / o[11],
+                 c->frozen_early_bits, c->frozen_stage_exchange_bits, c->frozen_xlane_bits, o[11], 0.01 * o[8] / o[11], 0.01 * o[9] / o[11], 0.01 * o[12] / o[11],
                  0.01 * (o[10] - o[8] - o[9] - o[12]) / o[11], 1.0e-5 * o[10]);
 #endif
     if (team) c->frozen_team_years++;

@@ -115,6 +115,10 @@
     const int xchg = (XCHG && by_col && own_bits == 48) ? uni_i(NK2D_FROZEN_XCHG_OF(A.coef_lds)) : 0;
     double* const xu0 = XCHG ? (double*)((char*)A.arrive + yr_xchg_offset(P.ncol)) : nullptr;
     (void)xchg; (void)xu0;
+    // option "frozen_xlane" (bit 10 of A.coef_lds, set by the host only on top of bit 9): the body whose cross-lane moves go through the VALU
+    constexpr bool XLANE = XCHG && NK2D_FROZEN_XLANE(E, KIND, TEAM, PIECES, LEAN);
+    const int xlane = (XLANE && xchg) ? uni_i(NK2D_FROZEN_XLANE_OF(A.coef_lds)) : 0;
+    (void)xlane;
 #define FZ_U (swapZ ? xu0 + 3 * nv : xu0)
 #define FZ_UN (swapZ ? xu0 : xu0 + 3 * nv)
     // first attempt of the year: Z0 = 0, W0 = 0 (radau.py:445-446)
@@ -293,7 +297,10 @@
                             if constexpr (XCHG) {
                             if (own_bits == 48 && xchg) {
                                 const StageXchg XC = {FZ_U, do_stage ? FZ_UN : FZ_U, 0};
-                                newton_fused_body<E, KIND, 0, 1, MPX, 1, 447>(P, FA, wave, lane, &Fin, &L, &own, &late, &XC); taken = true;
+                                if constexpr (XLANE) {
+                                    if (xlane) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 959>(P, FA, wave, lane, &Fin, &L, &own, &late, &XC); taken = true; }
+                                }
+                                if (!taken) { newton_fused_body<E, KIND, 0, 1, MPX, 1, 447>(P, FA, wave, lane, &Fin, &L, &own, &late, &XC); taken = true; }
                             }
                             }
                             if (taken) {}
@@ -334,7 +341,10 @@
                                 // (Z to memory where something reads it from there: the estimate and the end of a step that carries one,
                                 // the caller's commit of the last row)
                                 const StageXchg XC = {FZ_U, (do_stage && do_update) ? FZ_UN : FZ_U, (with_err || last_row) ? 1 : 0};
-                                newton_fused_body<E, KIND, 0, 1, MPX, 0, 447>(P, FA, wave, lane, nullptr, &L, &own, &late, &XC); taken = true;
+                                if constexpr (XLANE) {
+                                    if (xlane) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 959>(P, FA, wave, lane, nullptr, &L, &own, &late, &XC); taken = true; }
+                                }
+                                if (!taken) { newton_fused_body<E, KIND, 0, 1, MPX, 0, 447>(P, FA, wave, lane, nullptr, &L, &own, &late, &XC); taken = true; }
                             }
                             }
                             if (taken) {}

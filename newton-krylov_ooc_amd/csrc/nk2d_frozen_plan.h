@@ -28,6 +28,10 @@
 // piece flavour of the linear-source kind at seven levels per lane, where the body with the exchange beside the others makes the
 // compiler report a spilled register (<7, 0, 0, 1, 0>: that class stays on the body without it)
 #define NK2D_FROZEN_XCHG(E, KIND, TEAM, PIECES, LEAN) (NK2D_FROZEN_OWN(E, KIND, TEAM, LEAN) && !((E) == 7 && (KIND) == 0 && (PIECES)))
+// ... and of those the ones that carry the body whose cross-lane moves go through the VALU (option "frozen_xlane"; the moves
+// themselves: NK2D_FROZEN_XLANE_MOVES in nk2d_common.h): all but the piece flavour of the linear-source kind at six levels per
+// lane, where that body beside the others makes the compiler report a spilled register (<6, 0, 0, 1, 0>)
+#define NK2D_FROZEN_XLANE(E, KIND, TEAM, PIECES, LEAN) (NK2D_FROZEN_XCHG(E, KIND, TEAM, PIECES, LEAN) && !((E) == 6 && (KIND) == 0 && (PIECES)))
 
 // what of a context (nk2d_ctx) and its options the cache's arithmetic reads
 struct FrozenPlanIn {

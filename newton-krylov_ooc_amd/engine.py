@@ -249,6 +249,9 @@ class ModuleEngine:
         # the one-launch frozen year's neighbours exchange stage values instead of Z and Y (csrc/nk2d_frozen_body.inc)
         if "NK2D_FROZEN_STAGE_EXCHANGE" in os.environ:
             self.set_option("frozen_stage_exchange", float(os.environ["NK2D_FROZEN_STAGE_EXCHANGE"]))
+        # the one-launch frozen year's cross-lane moves in the VALU instead of through LDS (csrc/nk2d_common.h: the xl_ helpers)
+        if "NK2D_FROZEN_XLANE" in os.environ:
+            self.set_option("frozen_xlane", float(os.environ["NK2D_FROZEN_XLANE"]))
         # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_TWO_ENDED" in os.environ:
             self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
@@ -364,6 +367,20 @@ class ModuleEngine:
         host = np.empty((self.nz - 1, self.ny))
         self._chk(self._lib.nk2d_vmix_coeff(self._ctx, float(t), _dp(host)))
         return host
+
+    XLANE_SELFTEST_ROWS = 37
+
+    def xlane_selftest(self, v):
+        """(2, 37, 64): the 64 doubles `v` moved across one wave by __shfl ([0]) and by the VALU helpers ([1]); rows as
+        include/nk2d.h lists them at option "xlane_selftest_run" (the library's self-test: options in, counters out)"""
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        assert v.shape == (64,)
+        for lane in range(64):
+            self.set_option(f"xlane_selftest_in{lane}", float(v[lane]))
+        self.set_option("xlane_selftest_run", 1)
+        bits = np.array([[[self.counter(f"xlane_selftest_{w}_{row}_{lane}") for lane in range(64)]
+                          for row in range(self.XLANE_SELFTEST_ROWS)] for w in range(2)], dtype=np.int64)
+        return bits.view(np.float64)
 
     def jacobian_diags(self, t):
         """(5, tc, nz, ny): up, south, centre, north, down"""
