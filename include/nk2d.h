@@ -460,6 +460,16 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    the resident kernel that fits two waves to a SIMD -- 256 registers, the rest in scratch memory -- where that lets every
    (tracer, ypos) column be resident instead of several rounds of columns per command, 416 x 416: 1 248 columns; 2: wherever
    that flavour exists; 0: never.  Counters "stream_two_waves_kernel", "stream_columns_per_workgroup"),
+   "stream_xlane" (0, default, or 1; read at every start of the resident kernel, NK2D_STREAM_XLANE in the engines' environment:
+   the kernel runs every command -- Newton, error estimate, sweep, set-up, step boundary, Jacobian -- with its cross-lane moves
+   at distances 1 and 32 lanes and its sums over the wave as DPP and v_permlane32_swap in the VALU instead of ds_bpermute through
+   LDS: the vertical stencil of the tendencies, of the Jacobian diagonals and of the sinking flux, the first and last levels of
+   the parallel cyclic reductions of the line factorisation and of the solves, the norm partials; distances 2 to 16 stay on
+   ds_bpermute.  A flavour of the kernel of its own, never a run-time flag inside today's; every lane receives the same 64 bits:
+   the same year bit for bit, no decision, not part of the schedule fingerprint, no change of the kernel's shape.  Counter
+   "stream_xlane_bits": what the kernel launched last ran with -- 0 for linear sources at one level per lane (no such flavour:
+   it needs scratch memory where today's kernel needs none), 0 where the flavour would not keep every workgroup resident at
+   the shape the context has, 0 for a year from the tape ("frozen_tape"), whose kernel has today's body only),
    "stream_hist" (0, default, or 1; opt-in: the samples of nk2d_comp_fcn_hist in a year that runs as a command stream are
    COMMANDS of its resident kernel -- the dense output of the accepted step, packed, into a slot of a sample buffer in HBM,
    pushed right behind the step's boundary command, which such a step keeps -- instead of ending the kernel for a piece of

@@ -276,6 +276,12 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
         c->stream_hist_mb = value;
         return 0;
     }
+    if (key == "stream_xlane") {
+        // (no decision, no change of the resident kernel's shape: read at every start of the kernel, nk2d_stream.hip)
+        if (value != 0.0 && value != 1.0) return nk2d_fail(c, "nk2d_set_option: stream_xlane is 0 or 1");
+        c->stream_xlane = (int)value;
+        return 0;
+    }
     if (key == "stream_two_waves") {
         // (decides the shape of the resident kernel: taken before the context's first year as a command stream)
         if (c->strm) return nk2d_fail(c, "nk2d_set_option: stream_two_waves must be set before the first year of the context");
@@ -713,6 +719,8 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_stage_exchange_bits = 0;
     c->frozen_xlane = NK2D_FROZEN_XLANE_DEFAULT;
     c->frozen_xlane_bits = 0;
+    c->stream_xlane = 0;
+    c->stream_xlane_bits = 0;
     c->frozen_by_column = 1;
     c->strm = nullptr;
     c->spec_bias = 1.0;
@@ -1275,6 +1283,7 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_early_bits") v = c->frozen_early_bits;
     else if (key == "frozen_stage_exchange_bits") v = c->frozen_stage_exchange_bits;
     else if (key == "frozen_xlane_bits") v = c->frozen_xlane_bits;
+    else if (key == "stream_xlane_bits") v = c->stream_xlane_bits;
     else if (key == "frozen_step_sums_hash") v = c->frozen_step_sums_hash;
     else if (key == "frozen_lean_years") v = c->frozen_lean_years;
     else if (key == "frozen_forced_years") v = c->frozen_forced_years;

@@ -319,13 +319,13 @@ __device__ __forceinline__ void forced_sources(const DevP& P, const double* __re
 // phosphorus sources added to the transport tendency of tracer tr (0 po4, 1 dop, 2 pop) in the
 // reference's order (phosphorus.py:66-88): light- and po4-limited uptake, remineralisation of
 // dop and pop, sinking of pop.  po4 / dop / pop: the module's tracers at this wave's ypos column.
-template <int E>
+template <int E, int XL = 0>
 __device__ __forceinline__ void phos_tend(const DevP& P, int tr, int j, int lane, const double (&po4)[E],
                                           const double (&dop)[E], const double (&pop)[E], const double (&dzr)[E],
                                           double (&out)[E]) {
     double light[E], popprev[E];
     load_col<E>(P.LIGHT, j, lane, light);
-    shift_prev<E>(pop, popprev, lane, 0.0);
+    shift_prev<E, XL>(pop, popprev, lane, 0.0);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int k = lane * E + e;
@@ -366,43 +366,43 @@ __device__ __forceinline__ void phos_add(double (&u1)[E], double (&u2)[E], const
     for (int e = 0; e < E; ++e) { u1[e] = u1[e] + v1[e]; u2[e] = u2[e] + v2[e]; }
 }
 // phosphorus sources of tracer tr from its own values and the two others (in the order above)
-template <int E>
+template <int E, int XL = 0>
 __device__ __forceinline__ void phos_sources(const DevP& P, int tr, int j, int lane, const double (&own)[E],
                                              const double (&u1)[E], const double (&u2)[E], const double (&dzr)[E],
                                              double (&out)[E]) {
-    if (tr == 0) phos_tend<E>(P, 0, j, lane, own, u1, u2, dzr, out);
-    else if (tr == 1) phos_tend<E>(P, 1, j, lane, u1, own, u2, dzr, out);
-    else phos_tend<E>(P, 2, j, lane, u1, u2, own, dzr, out);
+    if (tr == 0) phos_tend<E, XL>(P, 0, j, lane, own, u1, u2, dzr, out);
+    else if (tr == 1) phos_tend<E, XL>(P, 1, j, lane, u1, own, u2, dzr, out);
+    else phos_tend<E, XL>(P, 2, j, lane, u1, u2, own, dzr, out);
 }
 
 // ---------------------------------------------------------------------------------
 // Jacobian planes (advection.py:111-173, horiz_mix.py:100-142, vert_mix.py:140-182)
 // up = d tend[k]/d c[k-1], dn = .../d c[k+1], south = .../d c[j-1], north = .../d c[j+1]
 // ---------------------------------------------------------------------------------
-template <int E, int MP>
+template <int E, int MP, int XL>
 __device__ __forceinline__ void jac_core(const DevP& P, const double (&kv)[E], const double* __restrict__ kvp,
                                          double* __restrict__ JL, double* __restrict__ JU, double* __restrict__ JS,
                                          double* __restrict__ JN, double* __restrict__ JC, const double* __restrict__ ylin,
                                          double* __restrict__ UPR, int task, int lane);
 
-template <int E, int MP = 0>
+template <int E, int MP = 0, int XL = 0>
 __device__ __forceinline__ void jac_body(const DevP& P, const double* __restrict__ kvp, double* __restrict__ JL,
                                          double* __restrict__ JU, double* __restrict__ JS, double* __restrict__ JN,
                                          double* __restrict__ JC, const double* __restrict__ ylin,
                                          double* __restrict__ UPR, int task, int lane) {
     double kv[E];
     load_col<E, MP>(kvp, task, lane, kv);
-    jac_core<E, MP>(P, kv, kvp, JL, JU, JS, JN, JC, ylin, UPR, task, lane);
+    jac_core<E, MP, XL>(P, kv, kvp, JL, JU, JS, JN, JC, ylin, UPR, task, lane);
 }
 
 // the five Jacobian diagonals of ypos column j (tracer independent part) from its vertical mixing column, in registers
-template <int E>
+template <int E, int XL = 0>
 __device__ __forceinline__ void jac_cols(const DevP& P, const double (&kv)[E], int j, int lane, double (&up)[E],
                                          double (&dn)[E], double (&so)[E], double (&no)[E], double (&ce)[E]) {
     ColCoef<E> cf;
     load_coef<E>(P, j, lane, cf);
     double kvprev[E];
-    shift_prev<E>(kv, kvprev, lane, 0.0);
+    shift_prev<E, XL>(kv, kvprev, lane, 0.0);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int k = lane * E + e;
@@ -463,14 +463,14 @@ __device__ __forceinline__ void phos_upr_col(const DevP& P, const double* __rest
 
 // the same from a vertical mixing column held in registers (kvp: its bundle in memory, read only for the source plane of
 // a forced module with a thresholded sink)
-template <int E, int MP = 0>
+template <int E, int MP = 0, int XL = 0>
 __device__ __forceinline__ void jac_core(const DevP& P, const double (&kv)[E], const double* __restrict__ kvp,
                                          double* __restrict__ JL, double* __restrict__ JU, double* __restrict__ JS,
                                          double* __restrict__ JN, double* __restrict__ JC, const double* __restrict__ ylin,
                                          double* __restrict__ UPR, int task, int lane) {
     const int j = task;
     double up[E], dn[E], so[E], no[E], ce[E];
-    jac_cols<E>(P, kv, j, lane, up, dn, so, no, ce);
+    jac_cols<E, XL>(P, kv, j, lane, up, dn, so, no, ce);
     store_col<E, MP>(JL, j, lane, up);
     store_col<E, MP>(JU, j, lane, dn);
     store_col<E, MP>(JS, j, lane, so);
@@ -659,7 +659,7 @@ __device__ __forceinline__ void factor_body(const DevP& P, const SweepArgs& A, i
     }
 }
 
-template <int E, int KIND, int MP = 0>
+template <int E, int KIND, int MP = 0, int XL = 0>
 __device__ __forceinline__ void sweep_body(const DevP& P, const SweepArgs& A, int task, int lane) {
     const int nvar = A.ntasks / P.ny, j = task / nvar, var = task - j * nvar;
     const bool is_c = var >= A.nreal / P.ny;
@@ -691,7 +691,7 @@ __device__ __forceinline__ void sweep_body(const DevP& P, const SweepArgs& A, in
         }
 #pragma unroll
         for (int e = 0; e < E; ++e) r[e] = ((lane * E + e) < P.nz) ? r[e] : 0.0;
-        tridiag_apply<E, double>(a, cc, inv, tab, r, lane);
+        tridiag_apply<E, double, XL>(a, cc, inv, tab, r, lane);
         store_col<E, MP>(A.xr_new, col, lane, r);
     } else {
         cplx r[E], inv[E], tab[NK2D_TAB];
@@ -726,7 +726,7 @@ __device__ __forceinline__ void sweep_body(const DevP& P, const SweepArgs& A, in
             const bool valid = (lane * E + e) < P.nz;
             r[e] = c_make(valid ? rr[e] : 0.0, valid ? ri[e] : 0.0);
         }
-        tridiag_apply<E, cplx>(a, cc, inv, tab, r, lane);
+        tridiag_apply<E, cplx, XL>(a, cc, inv, tab, r, lane);
 #pragma unroll
         for (int e = 0; e < E; ++e) { rr[e] = r[e].re; ri[e] = r[e].im; }
         store_col<E, MP>(A.xcr_new, col, lane, rr);
@@ -896,7 +896,9 @@ __device__ __forceinline__ void w_lds_put(double* s, int r, int lane, const doub
 //   bit 7  norm : the update part may form the norm partial behind its stores and leave it to the caller to store (LateNorm)
 //   bit 8  xchg : the neighbours exchange stage values U_i = Y + Z_i instead of Z_i and Y (StageXchg; on top of bits 4 and 5)
 //   bit 9  xlane: the cross-lane moves of the vertical stencil, of the two solves and of the norm partial go through the VALU
-//                 (the xl_ helpers of nk2d_common.h, option "frozen_xlane" of the one-launch year; only on top of CL 447)
+//                 (the xl_ helpers of nk2d_common.h, option "frozen_xlane" of the one-launch year on top of CL 447; option "stream_xlane" of the
+//                 command stream on top of its CL 0, 1 and 3 with MP = 1, where the line factorisation and the phosphorus sources
+//                 take their moves from the helpers too)
 struct LdsSrc {
     const double* coef;
     double* w;
@@ -967,8 +969,12 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
                                                   OwnState<E>* own = nullptr, LateNorm* late = nullptr,
                                                   const StageXchg* xc = nullptr) {
     static_assert(!(CL & 256) || (CL & 48) == 48, "the stage-value exchange needs the column's whole own state");
-    static_assert(!(CL & 512) || (CL & 511) == 447, "the VALU cross-lane moves exist on top of the stage-value exchange only");
+    static_assert(!(CL & 512) || (CL & 511) == 447 || (MP == 1 && ((CL & 511) == 0 || (CL & 511) == 1 || (CL & 511) == 3)),
+                  "the VALU cross-lane moves exist on top of the stage-value exchange and in the command stream's three flavours only");
     constexpr int XL = (CL & 512) ? NK2D_FROZEN_XLANE_MOVES : 0;
+    // (the command stream's flavours take the factorisation and the phosphorus sources from the helpers too; the one-launch year's
+    // body, CL 447, is the text it was)
+    constexpr int XS = ((CL & 511) == 447) ? 0 : XL;
     const double* coef_lds = (CL & 1) ? lds->coef : nullptr;
     double* w_lds = (CL & 2) ? lds->w : nullptr;
     (void)coef_lds; (void)w_lds;
@@ -1051,7 +1057,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
                 phos_load_others<E>(P, tr, j, lane, A.st.y, u1, u2);
                 phos_load_others<E>(P, tr, j, lane, A.st.z + i * A.st.nv, v1, v2);
                 phos_add<E>(u1, u2, v1, v2);
-                phos_sources<E>(P, tr, j, lane, c, u1, u2, cf.dzr, f);
+                phos_sources<E, XS>(P, tr, j, lane, c, u1, u2, cf.dzr, f);
             }
 #pragma unroll
             for (int e = 0; e < E; ++e) {
@@ -1130,7 +1136,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
         if constexpr (FACTOR) {
             double dre[E];
             line_diag<E, KIND, MP>(P, A.sw.JC, tr, j, lane, A.sw.cre, dre);
-            tridiag_factor<E, double>(a, cc, dre, inv, tab, lane);
+            tridiag_factor<E, double, XS>(a, cc, dre, inv, tab, lane);
             store_col<E>(A.sw.fr_inv, task, lane, inv);
             double* p = A.sw.fr_tab + (size_t)task * (NK2D_TAB * 64) + lane;
 #pragma unroll
@@ -1160,7 +1166,7 @@ __device__ __forceinline__ void newton_fused_body(const DevP& P, const FusedArgs
             line_diag<E, KIND, MP>(P, A.sw.JC, tr, j, lane, A.sw.ccr, dre);
 #pragma unroll
             for (int e = 0; e < E; ++e) d[e] = c_make(dre[e], ((lane * E + e) < P.nz) ? A.sw.cci : 0.0);
-            tridiag_factor<E, cplx>(a, cc, d, inv, tab, lane);
+            tridiag_factor<E, cplx, XS>(a, cc, d, inv, tab, lane);
             double re[E], im[E];
 #pragma unroll
             for (int e = 0; e < E; ++e) { re[e] = inv[e].re; im[e] = inv[e].im; }
@@ -1871,7 +1877,7 @@ struct ErrArgs {
     int last;              // this launch ends the solve
 };
 
-template <int E, int KIND, int MP = 0>
+template <int E, int KIND, int MP = 0, int XL = 0>
 __device__ __forceinline__ void err_fused_body(const DevP& P, const ErrArgs& A, int task, int lane) {
     const int tr = task / P.ny, j = task - tr * P.ny;
     double r[E], x1[E], a[E], cc[E];
@@ -1914,7 +1920,7 @@ __device__ __forceinline__ void err_fused_body(const DevP& P, const ErrArgs& A, 
         load_tab<E>(A.sw.fr_tab, task, lane, tab);
 #pragma unroll
         for (int e = 0; e < E; ++e) r[e] = ((lane * E + e) < P.nz) ? r[e] : 0.0;
-        tridiag_apply<E, double>(a, cc, inv, tab, r, lane);
+        tridiag_apply<E, double, XL>(a, cc, inv, tab, r, lane);
     }
     if (A.stage == 1) {
 #pragma unroll
@@ -1933,12 +1939,13 @@ __device__ __forceinline__ void err_fused_body(const DevP& P, const ErrArgs& A, 
         const double q = r[e] / sc;
         acc += q * q;
     }
-    acc = wave_sum(acc);
+    if constexpr ((XL & NK2D_XL_SUM) != 0) acc = xl_wave_sum(acc);
+    else acc = wave_sum(acc);
     if (lane == 0) st_mp<MP>(A.part + task, acc);
 }
 
 // filtered error estimate right-hand side  fun(t, y + error) + Z^T E / h  (radau.py:485-487)
-template <int E, int KIND, int MP = 0>
+template <int E, int KIND, int MP = 0, int XL = 0>
 __device__ __forceinline__ void err_rhs2_body(const DevP& P, const double* __restrict__ y, const double* __restrict__ err,
                                               const double* __restrict__ kvp, const double* __restrict__ z, size_t nv,
                                               double h, double* __restrict__ out, int task, int lane) {
@@ -1960,14 +1967,14 @@ __device__ __forceinline__ void err_rhs2_body(const DevP& P, const double* __res
 #pragma unroll
     for (int e = 0; e < E; ++e) cn[e] = cn[e] + t0[e];
     load_col<E, MP>(kvp, j, lane, kv);
-    tend_col<E, KIND>(P, cf, c, cs, cn, kv, tr, lane, ff);
+    tend_col<E, KIND, XL>(P, cf, c, cs, cn, kv, tr, lane, ff);
     if constexpr (KIND == 2) forced_sources<E>(P, kvp, j, lane, c, ff);
     if constexpr (KIND == 1) {
         double u1[E], u2[E], v1[E], v2[E];
         phos_load_others<E>(P, tr, j, lane, y, u1, u2);
         phos_load_others<E>(P, tr, j, lane, err, v1, v2);
         phos_add<E>(u1, u2, v1, v2);
-        phos_sources<E>(P, tr, j, lane, c, u1, u2, cf.dzr, ff);
+        phos_sources<E, XL>(P, tr, j, lane, c, u1, u2, cf.dzr, ff);
     }
     double z0[E], z1[E], z2[E];
     load_col<E, MP>(z, task, lane, z0);
@@ -1983,7 +1990,7 @@ __device__ __forceinline__ void err_rhs2_body(const DevP& P, const double* __res
 
 // accepted step: y_new = y + Z2 and f_new = fun(t_new, y_new) in one pass (radau.py:509-521); the
 // lateral neighbours' y_new are formed on the fly, each wave stores its own column
-template <int E, int KIND, int MP = 0>
+template <int E, int KIND, int MP = 0, int XL = 0>
 __device__ __forceinline__ void commit_tend_body(const DevP& P, const double* __restrict__ y, const double* __restrict__ z2,
                                                  const double* __restrict__ kvp, double* __restrict__ ynew,
                                                  double* __restrict__ f, int task, int lane) {
@@ -2006,14 +2013,14 @@ __device__ __forceinline__ void commit_tend_body(const DevP& P, const double* __
 #pragma unroll
     for (int e = 0; e < E; ++e) cn[e] = cn[e] + t0[e];
     load_col<E, MP>(kvp, j, lane, kv);
-    tend_col<E, KIND>(P, cf, c, cs, cn, kv, tr, lane, ff);
+    tend_col<E, KIND, XL>(P, cf, c, cs, cn, kv, tr, lane, ff);
     if constexpr (KIND == 2) forced_sources<E>(P, kvp, j, lane, c, ff);
     if constexpr (KIND == 1) {
         double u1[E], u2[E], v1[E], v2[E];
         phos_load_others<E>(P, tr, j, lane, y, u1, u2);
         phos_load_others<E>(P, tr, j, lane, z2, v1, v2);
         phos_add<E>(u1, u2, v1, v2);
-        phos_sources<E>(P, tr, j, lane, c, u1, u2, cf.dzr, ff);
+        phos_sources<E, XL>(P, tr, j, lane, c, u1, u2, cf.dzr, ff);
     }
     store_col<E>(f, task, lane, ff);
 }
@@ -2034,7 +2041,7 @@ struct BoundaryArgs {
 };
 
 // sum((err / (atol + max(|y|, |y + Z2|) rtol))^2)  (radau.py:480-481)
-template <int E, int MP = 0>
+template <int E, int MP = 0, int XL = 0>
 __device__ __forceinline__ void err_norm_body(const DevP& P, const double* __restrict__ y, const double* __restrict__ z2p,
                                               const double* __restrict__ err, double* __restrict__ part, int task, int lane) {
     double yy[E], z2[E], er[E];
@@ -2049,7 +2056,8 @@ __device__ __forceinline__ void err_norm_body(const DevP& P, const double* __res
         const double a = er[e] / sc;
         acc += a * a;
     }
-    acc = wave_sum(acc);
+    if constexpr ((XL & NK2D_XL_SUM) != 0) acc = xl_wave_sum(acc);
+    else acc = wave_sum(acc);
     if (lane == 0) st_mp<MP>(part + task, acc);
 }
 

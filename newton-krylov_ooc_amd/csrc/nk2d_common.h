@@ -56,6 +56,8 @@ struct nk2d_ctx {
     struct nk2d_stream_state* strm;
     int stream_years;      // option "stream_years": 1 = forward years of eligible contexts run as command streams
     int stream_two_waves;  // option "stream_two_waves": the 256-register flavour of the kernel where it lets every column be resident
+    int stream_xlane;      // option "stream_xlane": the resident kernel's cross-lane moves at distances 1 and 32 and its wave sums in the VALU
+    int stream_xlane_bits; // counter "stream_xlane_bits": what the resident kernel launched last ran with
     int stream_on;         // set by the integrator for the span of a year that may run as a command stream
     int stream_lost;       // years in a row whose kernel gave up (two: the context stops trying)
     int64_t stream_cmds, stream_launches, stream_timeouts, stream_years_run;   // counters (nk2d_get_counter)
@@ -661,7 +663,42 @@ __device__ __forceinline__ void store_col(double* __restrict__ base, size_t col,
 // ---------------------------------------------------------------------------------
 #define NK2D_TAB 14
 
-template <int E, typename T>
+// both directions of one value at distance S with the helper family XL (the lane's own value where it has no partner, either way)
+template <int XL, int S, typename T>
+__device__ __forceinline__ void xl_sel_both(T v, T& up, T& dn) {
+    if constexpr ((XL & S) != 0) {
+        if constexpr (sizeof(T) == sizeof(double)) {
+            xl_both<S>(v, up, dn);
+        } else {
+            xl_both<S>(v.re, up.re, dn.re);
+            xl_both<S>(v.im, up.im, dn.im);
+        }
+    } else {
+        up = shfl_up_t(v, S);
+        dn = shfl_down_t(v, S);
+    }
+}
+// one level of tridiag_factor's parallel cyclic reduction with the helper family XL: the expressions of its loop, S a constant
+template <int XL, int S, typename T>
+__device__ __forceinline__ void pcr_factor_level(T& A, T& B, T& C, T& k1o, T& k2o, int lane) {
+    T iB = t_recip(B);
+    T Am, iBm, Cm, Ap, iBp, Cp;
+    xl_sel_both<XL, S>(A, Am, Ap);
+    xl_sel_both<XL, S>(iB, iBm, iBp);
+    xl_sel_both<XL, S>(C, Cm, Cp);
+    const bool hm = lane >= S, hp = lane + S < 64;
+    T k1 = hm ? t_mul(A, iBm) : t_zero(T());
+    T k2 = hp ? t_mul(C, iBp) : t_zero(T());
+    if (!hm) { Am = t_zero(T()); Cm = t_zero(T()); }
+    if (!hp) { Ap = t_zero(T()); Cp = t_zero(T()); }
+    k1o = k1;
+    k2o = k2;
+    B = t_nfma(t_nfma(B, Cm, k1), Ap, k2);
+    A = t_neg(t_mul(Am, k1));
+    C = t_neg(t_mul(Cp, k2));
+}
+
+template <int E, typename T, int XL = 0>
 __device__ __forceinline__ void tridiag_factor(const double (&a)[E], const double (&c)[E], const T (&d)[E],
                                                T (&inv)[E], T (&tab)[NK2D_TAB], int lane) {
     T al[E], be[E];
@@ -686,7 +723,7 @@ __device__ __forceinline__ void tridiag_factor(const double (&a)[E], const doubl
             al[i] = t_nfma(al[i], m, al[i + 1]);
             be[i] = t_neg(t_mul(m, be[i + 1]));
         }
-        T n_al = shfl_down_t(al[0], 1), n_inv = shfl_down_t(inv[0], 1), n_be = shfl_down_t(be[0], 1);
+        T n_al = xl_sel_down<XL, 1>(al[0]), n_inv = xl_sel_down<XL, 1>(inv[0]), n_be = xl_sel_down<XL, 1>(be[0]);
         G = t_mulr(n_inv, c[E - 1]);
         A = al[E - 1];
         B = t_nfma(dlast, G, n_al);
@@ -697,6 +734,14 @@ __device__ __forceinline__ void tridiag_factor(const double (&a)[E], const doubl
         B = d[0];
         C = t_from_real(c[0], T());
     }
+    if constexpr (XL != 0) {
+        pcr_factor_level<XL, 1>(A, B, C, tab[0], tab[6], lane);
+        pcr_factor_level<XL, 2>(A, B, C, tab[1], tab[7], lane);
+        pcr_factor_level<XL, 4>(A, B, C, tab[2], tab[8], lane);
+        pcr_factor_level<XL, 8>(A, B, C, tab[3], tab[9], lane);
+        pcr_factor_level<XL, 16>(A, B, C, tab[4], tab[10], lane);
+        pcr_factor_level<XL, 32>(A, B, C, tab[5], tab[11], lane);
+    } else {
     int lv = 0;
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1, ++lv) {
@@ -713,6 +758,7 @@ __device__ __forceinline__ void tridiag_factor(const double (&a)[E], const doubl
         B = t_nfma(t_nfma(B, Cm, k1), Ap, k2);
         A = t_neg(t_mul(Am, k1));
         C = t_neg(t_mul(Cp, k2));
+    }
     }
     tab[12] = t_recip(B);
     tab[13] = G;

@@ -89,6 +89,18 @@ struct StreamCmd {
 #define NK2D_RING_SLOTS 256
 static_assert(sizeof(StreamCmd) <= 4 * NK2D_CMD_DWORDS, "a command must fit a ring slot");
 
+// Option "stream_xlane": the classes (levels per lane E, module kind, W2 = the two-waves flavour k_stream_w2) whose resident kernel
+// exists in the flavour whose cross-lane moves at distances 1 and 32, and wave sums, go through the VALU (template parameter XL of
+// stream_body; the tape flavour never).  A class left out here runs today's kernel and reports counter "stream_xlane_bits" 0:
+// the ones whose XL flavour needs more scratch memory than their XL = 0 sibling.
+// Left out: linear sources at one level per lane, one wave to a SIMD -- 20 bytes of scratch per lane against none
+// (profiles/r19_stream_xlane_resources.log).
+#define NK2D_STREAM_XLANE(E, KIND, W2) (!((E) == 1 && (KIND) == 0 && !(W2)))
+
+// (the two-waves flavour is instantiated where it can matter: state-dependent sources from five levels per lane)
+template <int E, int KIND>
+constexpr bool kStreamHasTwoWaves = KIND == 1 && E >= 5;
+
 struct StreamArgs {
     const unsigned long long* h_ring;   // pinned host memory: what the host pushes
     unsigned long long* d_ring;         // HBM: what the relay wave has forwarded
@@ -150,3 +162,8 @@ unsigned nk2d_stream_last_seq(const nk2d_ctx* c);
 // the tape: upload after recording, run (0; NK2D_RC_STREAM_LOST when the kernel gave up, 1 when it cannot be resident)
 int nk2d_tape_upload(nk2d_ctx* c, nk2d_tape* T);
 int nk2d_tape_run(nk2d_ctx* c, nk2d_tape* T);
+#ifdef __HIPCC__
+// nk2d_stream_xl.hip: the host-fed resident kernel in the flavour of option "stream_xlane", launched on the context's stream -- or,
+// with max_blocks, the occupancy query for it; hipErrorInvalidValue for a class NK2D_STREAM_XLANE leaves out
+hipError_t nk2d_stream_launch_xl(nk2d_ctx* c, dim3 grid, dim3 block, DevP& P, StreamArgs& A, int* max_blocks, size_t lds_bytes, bool two_waves);
+#endif

@@ -252,6 +252,10 @@ class ModuleEngine:
         # the one-launch frozen year's cross-lane moves in the VALU instead of through LDS (csrc/nk2d_common.h: the xl_ helpers)
         if "NK2D_FROZEN_XLANE" in os.environ:
             self.set_option("frozen_xlane", float(os.environ["NK2D_FROZEN_XLANE"]))
+        # the command-stream year's cross-lane moves at distances 1 and 32, and its wave sums, in the VALU (csrc/nk2d_stream.hip),
+        # read at every start of the resident kernel
+        if "NK2D_STREAM_XLANE" in os.environ:
+            self.set_option("stream_xlane", float(os.environ["NK2D_STREAM_XLANE"]))
         # block elimination of the preconditioner from both ends of the ypos axis (csrc/nk2d_precond.hip), read at its set-up
         if "NK2D_PC_TWO_ENDED" in os.environ:
             self.set_option("pc_two_ended", float(os.environ["NK2D_PC_TWO_ENDED"]))
