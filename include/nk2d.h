@@ -274,6 +274,9 @@ int nk2d_frozen_resumes(nk2d_ctx* ctx, int64_t* n);
    "frozen_stage_exchange_bits" (option "frozen_stage_exchange" as in effect in that year, under the same rule -- and 0 whatever the
    option says for linear sources at seven levels per lane on a cache in pieces, whose kernel has no body for it),
    "frozen_xlane_bits" (option "frozen_xlane" as in effect in that year: 0 wherever "frozen_stage_exchange_bits" is 0),
+   "frozen_dedicated_bits" (option "frozen_dedicated" as in effect in that year: 1 or 2 only where the year ran in the kernel that
+   carries the default year's body alone), "frozen_dedicated_years" (one-launch years that kernel ran; also counted in
+   "frozen_persistent_years"),
    "frozen_step_sums_hash" (64-bit FNV-1a hash of the bits of the step sums the last whole-year check of a frozen year read: the
    norm sums of every step's last Newton iteration and of the one before -- the same for the same year by whatever path),
    "frozen_forced_years" (one-launch years only option "frozen_forced" made possible; also counted in "frozen_persistent_years",
@@ -533,6 +536,13 @@ int nk2d_set_norm_hook_vec(nk2d_ctx* ctx, nk2d_norm_hook_vec_fn fn, void* user, 
    of the tendencies, the parallel cyclic reduction of the two tridiagonal solves, the sum of the norm partial -- with DPP and
    v_permlane swaps in the VALU instead of ds_bpermute through LDS; every lane receives the same 64 bits: the same year bit for
    bit; no decision, not part of the schedule fingerprint; counter "frozen_xlane_bits"),
+   "frozen_dedicated" (0, 1 or 2, anything else is an error; default 2; read at every frozen year: a year that would run the Newton
+   body of every default -- all of the column in LDS and registers, "frozen_early", the stage-value exchange and the VALU moves in
+   effect: linear sources at five to seven levels per lane on the full cache, "frozen_lds_bits" 63 -- runs in k_frozen_persistent_d, the
+   same kernel text compiled with that one body instead of twenty and with what the host guarantees for it as constants; 2: and
+   its hand-over polls the two neighbours' flags and the abort flag with one load per spin; the same device functions: the same
+   year bit for bit; no decision, not part of the schedule fingerprint or the cache key; counters "frozen_dedicated_bits",
+   "frozen_dedicated_years"),
    "xlane_selftest_in0" .. "xlane_selftest_in63" and "xlane_selftest_run" (the self-test of those moves, no entry point of its own:
    the 64 doubles of one wave, lane by lane, then 1 to run it: one wave moves them -- as a complex value too: that vector and
    the same vector read backwards -- by 1, 2, 4, 8, 16 and 32 lanes; counter "xlane_selftest_<w>_<row>_<lane>" is then the 64 bits

@@ -256,6 +256,12 @@ extern "C" int nk2d_set_option(nk2d_ctx* c, const char* name, double value) {
     if (key == "frozen_early") { c->frozen_early = (int)value != 0 ? 1 : 0; return 0; }
     if (key == "frozen_stage_exchange") { c->frozen_stage_exchange = (int)value != 0 ? 1 : 0; return 0; }
     if (key == "frozen_xlane") { c->frozen_xlane = (int)value != 0 ? 1 : 0; return 0; }
+    if (key == "frozen_dedicated") {
+        // the one-launch year in the entry that carries the default year's body alone (nk2d_frozen_d.hip); read at every frozen year
+        if (value != 0.0 && value != 1.0 && value != 2.0) return nk2d_fail(c, "nk2d_set_option: frozen_dedicated is 0, 1 or 2");
+        c->frozen_dedicated = (int)value;
+        return 0;
+    }
     if (key == "frozen_by_column") { c->frozen_by_column = (int)value; return 0; }
     if (key == "frozen_cache_after") { c->frozen_cache_after = (int)value; return 0; }
     if (key == "spec_bias") { c->spec_bias = value > 0.0 ? value : 1.0; return 0; }
@@ -719,6 +725,9 @@ static int create_impl(nk2d_ctx* c, const nk2d_desc* desc) {
     c->frozen_stage_exchange_bits = 0;
     c->frozen_xlane = NK2D_FROZEN_XLANE_DEFAULT;
     c->frozen_xlane_bits = 0;
+    c->frozen_dedicated = NK2D_FROZEN_DEDICATED_DEFAULT;
+    c->frozen_dedicated_bits = 0;
+    c->frozen_dedicated_years = 0;
     c->stream_xlane = 0;
     c->stream_xlane_bits = 0;
     c->frozen_by_column = 1;
@@ -1283,6 +1292,8 @@ extern "C" int nk2d_get_counter(nk2d_ctx* c, const char* name, int64_t* out) {
     else if (key == "frozen_early_bits") v = c->frozen_early_bits;
     else if (key == "frozen_stage_exchange_bits") v = c->frozen_stage_exchange_bits;
     else if (key == "frozen_xlane_bits") v = c->frozen_xlane_bits;
+    else if (key == "frozen_dedicated_bits") v = c->frozen_dedicated_bits;
+    else if (key == "frozen_dedicated_years") v = c->frozen_dedicated_years;
     else if (key == "stream_xlane_bits") v = c->stream_xlane_bits;
     else if (key == "frozen_step_sums_hash") v = c->frozen_step_sums_hash;
     else if (key == "frozen_lean_years") v = c->frozen_lean_years;

@@ -2210,6 +2210,45 @@ struct NeighbourSync {
         if (fences) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         return *lds_ok != 0;
     }
+    // wait() with ONE agent-scope load per spin (k_frozen_persistent_d with option "frozen_dedicated" 2, and no other kernel): lanes
+    // 0 and 1 read the neighbours' flags, lane 2 the abort flag, in the same instruction -- a spin that does not match is one
+    // round trip through the fabric, not two.  The abort flag's value is looked at where wait() looks at it: behind a poll that
+    // did not match.  Match, time limit, spin limit, raising the flag, lds_ok and the two joins: wait()'s statements
+    __device__ __forceinline__ bool wait_one_load() {
+        if (threadIdx.x < 64) {
+            const int lane = threadIdx.x;
+            const int other = (lane == 0) ? left : ((lane == 1) ? right : -1);
+            const unsigned* const src = (lane == 2) ? (const unsigned*)abort_flag : ((other >= 0) ? flags + (size_t)other * 32 : nullptr);
+            int good = 1;
+            long long spins = 0;
+            const long long t_begin = (long long)__builtin_amdgcn_s_memrealtime();
+            for (;;) {
+                unsigned got = 0;
+                if (src != nullptr) got = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned v = (other >= 0) ? got : phase;
+                if (__all((int)(v >= phase))) break;
+                const int ab = __builtin_amdgcn_readlane((int)got, 2);
+                const bool late = ((++spins & 63) == 0 || spin_ticks == 0) &&
+                                  (long long)__builtin_amdgcn_s_memrealtime() - t_begin > spin_ticks;
+                if (late || spins > 4000LL * NK2D_SPIN_LIMIT || ab != 0) {
+                    if (lane == 0) __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    good = 0;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(1);
+            }
+            if (lane == 0) *lds_ok = good;
+#ifdef NK2D_FROZEN_CLOCKS
+            ck_wait += (long long)__builtin_amdgcn_s_memrealtime() - ck_flag;
+#endif
+        }
+        __syncthreads();
+#ifdef NK2D_FROZEN_CLOCKS
+        ck_match = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
+        if (fences) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        return *lds_ok != 0;
+    }
     // publish(); wait(); for every caller that has nothing to do in between -- as one text, the one it always was: composed of
     // the two halves, the kernels that call it came out of the compiler with other register counts
     // (profiles/r11_frozen_early_kernel_resources.log).  The same statements as publish() and wait(): a change goes into both
@@ -2528,6 +2567,9 @@ struct FrozenPieceArgs : FrozenArgs {
 };
 template <int PIECES> struct FrozenArgOf { typedef FrozenArgs type; };
 template <> struct FrozenArgOf<1> { typedef FrozenPieceArgs type; };
+// k_frozen_persistent_d (nk2d_frozen_d.hip: the body of the default year alone, option "frozen_dedicated"), launched on the context's
+// stream -- or, with max_blocks, only asked for its occupancy.  hipErrorInvalidValue: no such instantiation
+hipError_t nk2d_frozen_launch_d(nk2d_ctx* c, dim3 grid, dim3 block, DevP& P, FrozenPieceArgs& A, bool pieces, int* max_blocks, size_t lds_bytes);
 
 // f = fun(t, y) of the column (the plane kvp is the mixing plane at t): the tendency at a step start, for the error estimate
 template <int E, int KIND, int MP>

@@ -38,6 +38,9 @@
 #define NK2D_FROZEN_STAGE_EXCHANGE_DEFAULT 1
 // option "frozen_xlane" as a context starts with it (1: the cross-lane moves of the one-launch year's Newton phase go through the VALU)
 #define NK2D_FROZEN_XLANE_DEFAULT 1
+// option "frozen_dedicated" as a context starts with it (0: k_frozen_persistent; 1: the entry that carries the default year's body alone,
+// k_frozen_persistent_d; 2: that entry with the hand-over's one-load poll)
+#define NK2D_FROZEN_DEDICATED_DEFAULT 2
 // ... and which moves that body takes from the xl_ helpers: the sum of the distances (1 | 2 | 4 | 8 | 16 | 32) and NK2D_XL_SUM (64)
 #ifndef NK2D_FROZEN_XLANE_MOVES
 #define NK2D_FROZEN_XLANE_MOVES 97
@@ -159,6 +162,9 @@ struct nk2d_ctx {
     int frozen_stage_exchange_bits; // counter "frozen_stage_exchange_bits": the option in effect in the one-launch year launched last
     int frozen_xlane;               // option "frozen_xlane": the Newton phase of the one-launch year moves values between lanes in the VALU, not through LDS
     int frozen_xlane_bits;          // counter "frozen_xlane_bits": the option in effect in the one-launch year launched last
+    int frozen_dedicated;           // option "frozen_dedicated": 1, 2 the one-launch year in the entry with the default year's body alone (2: one-load poll)
+    int frozen_dedicated_bits;      // counter "frozen_dedicated_bits": the option in effect in the one-launch year launched last (frozen_dedicated())
+    int64_t frozen_dedicated_years; // counter "frozen_dedicated_years": one-launch years that entry ran (also counted in frozen_persistent_years)
     int frozen_by_column; // option "frozen_by_column": a workgroup of the one-launch year is one ypos column with all its tracers
     int frozen_alloc_async;   // option "frozen_alloc_async": a schedule cache above 8 GB is allocated by a thread of its own
     int frozen_cache_after;   // option "frozen_cache_after": frozen years of a schedule that run launch by launch before its cache is built (default 0; -1: 0 for a cache below 8 GB, 3 above)

@@ -124,7 +124,9 @@ __device__ __forceinline__ void frozen_factor_phase(const DevP& P, const FusedAr
 // those NK2D_FROZEN_OWN names (nk2d_frozen_plan.h: the macro the planner fits the LDS with).
 template <int E, int KIND, int TEAM = 0, int PIECES = 0, int LEAN = 0>
 __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typename FrozenArgOf<PIECES>::type A) {
+#define FZ_ONLY 0
 #include "nk2d_frozen_body.inc"
+#undef FZ_ONLY
 }
 // The same within 256 registers, so that a SIMD holds TWO waves (option "frozen_phosphorus" 2 and 3; phosphorus on the lean cache from
 // five levels per lane, where a by-column workgroup of three waves at a wave per SIMD leaves the chip room for one workgroup per
@@ -132,7 +134,9 @@ __global__ void __launch_bounds__(NK2D_BLOCK) k_frozen_persistent(DevP P, typena
 template <int E, int PIECES>
 __global__ void __launch_bounds__(NK2D_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) k_frozen_persistent_w2(DevP P, typename FrozenArgOf<PIECES>::type A) {
     constexpr int KIND = 1, TEAM = 0, LEAN = 1;
+#define FZ_ONLY 0
 #include "nk2d_frozen_body.inc"
+#undef FZ_ONLY
 }
 
 // ---- the store: everything a schedule fixes besides the state, kept for the schedule `key`; rebuilt when another schedule comes.
@@ -339,6 +343,21 @@ static hipError_t launch_resident(nk2d_ctx* c, K kernel, dim3 grid, dim3 block, 
     }
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, nk2d_s(c), P, A);
     return hipGetLastError();
+}
+
+// the same for k_frozen_persistent_d, which lives in a unit of its own (nk2d_frozen_d.hip): always by column, everything in LDS
+static hipError_t launch_resident_dedicated(nk2d_ctx* c, bool pieces, DevP& P, FrozenPieceArgs& A) {
+    if (!A.by_column || c->tc > NK2D_WAVES_PER_BLOCK) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)c->ny), block((unsigned)(64 * c->tc));
+    const size_t lds_bytes = sizeof(double) * frozen_lds_doubles(c->E, A.coef_lds, true, c->tc);
+    int per_cu = 0;
+    hipError_t rc = nk2d_frozen_launch_d(c, grid, block, P, A, pieces, &per_cu, lds_bytes);
+    if (rc != hipSuccess) return rc;
+    hipDeviceProp_t prop;
+    rc = hipGetDeviceProperties(&prop, c->dev);
+    if (rc != hipSuccess) return rc;
+    if ((long long)per_cu * prop.multiProcessorCount < (long long)grid.x) return hipErrorCooperativeLaunchTooLarge;
+    return nk2d_frozen_launch_d(c, grid, block, P, A, pieces, nullptr, lds_bytes);
 }
 
 template <int E, int KIND, int TEAM, int PIECES, int LEAN>
@@ -736,6 +755,12 @@ static int frozen_year_args(nk2d_ctx* c, const nk2d_frozen_cache* fc, const Froz
     c->frozen_xlane_bits =
         (c->frozen_stage_exchange_bits != 0 && NK2D_FROZEN_XLANE(c->E, c->kind, team_year, pl.pieces, pl.lean)) ? c->frozen_xlane : 0;
     A.coef_lds |= c->frozen_xlane_bits << 10;
+    // option "frozen_dedicated": where all of the above say CL 959, the entry that carries that body alone (frozen_dedicated(): the rule;
+    // frozen_launch_year() takes it from the counter).  Bit 11, read by that entry only: its hand-over polls with one load.  No
+    // decision, not part of the schedule fingerprint or the cache key
+    c->frozen_dedicated_bits = frozen_dedicated(c->frozen_dedicated, c->E, c->kind, team_year, pl.pieces, pl.lean, c->frozen_lds_bits,
+                                                c->frozen_early_bits, c->frozen_stage_exchange_bits, c->frozen_xlane_bits);
+    if (c->frozen_dedicated_bits == 2) A.coef_lds |= 1 << 11;
     return 0;
 }
 
@@ -759,7 +784,8 @@ static int frozen_launch_year(nk2d_ctx* c, const FrozenPlan& pl, int64_t n, DevP
         } turn(team ? 4 * c->ncol : c->ncol);
         hipError_t rc = hipErrorInvalidValue;
         bool two = false;
-        if (pl.phos) rc = launch_frozen_phos_flavour(c, pl.pieces, P, A, false, &two);
+        if (c->frozen_dedicated_bits != 0) rc = launch_resident_dedicated(c, pl.pieces, P, A);
+        else if (pl.phos) rc = launch_frozen_phos_flavour(c, pl.pieces, P, A, false, &two);
         else if (pl.lean) rc = pl.pieces ? launch_frozen<1, 1>(c, team, grid, P, A) : launch_frozen<0, 1>(c, team, grid, P, static_cast<FrozenArgs&>(A));
         else rc = pl.pieces ? launch_frozen<1, 0>(c, team, grid, P, A) : launch_frozen<0, 0>(c, team, grid, P, static_cast<FrozenArgs&>(A));
         c->frozen_two_waves_last = two ? 1 : 0;

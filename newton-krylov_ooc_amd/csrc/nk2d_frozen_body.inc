@@ -1,5 +1,13 @@
 // nk2d_frozen_body.inc -- the body of the one-launch frozen year's kernel (nk2d_frozen.hip): included inside k_frozen_persistent and
 // k_frozen_persistent_w2, which name E, KIND, TEAM, PIECES, LEAN and the arguments P and A.  Not a header: no guard, no declarations.
+// The includer also names FZ_ONLY.  0: the text as it always was -- every body of the ladder, picked at run time from A.coef_lds.
+// 959 (k_frozen_persistent_d, nk2d_frozen_d.hip): the body of the default year alone, CL 959, and what the host guarantees for
+// that body (frozen_dedicated(), nk2d_frozen_plan.h) as compile-time truth: by column; W, the step block, the pivots and Y in
+// LDS; the whole own state; "frozen_early", the stage-value exchange and the VALU moves on.  Bit 11 of A.coef_lds then picks the
+// hand-over's poll.  Every `#if FZ_ONLY` below leaves the 0 text token for token what it was.
+#if FZ_ONLY
+    static_assert(FZ_ONLY == 959 && !TEAM && !LEAN && NK2D_FROZEN_OWN(E, KIND, TEAM, LEAN), "the dedicated entry: the one body of the default year");
+#endif
     constexpr int XCD = 0, NB = 1;      // (rounds 2 - 3 also had all workgroups on one XCD and a grid barrier between the phases)
     __shared__ int lds_ok;
     __shared__ double team_lds[TEAM ? sizeof(TeamLds<E, 3>) / sizeof(double) : 1];
@@ -10,7 +18,12 @@
     // the column of this wave.  A team: the workgroup's.  A wave per column: adjacent columns of one tracer to a workgroup, or
     // -- `by_column` -- the workgroup is ONE ypos column and its waves that column's tracers (what is the same for every tracer
     // of a ypos column is then shared through LDS)
+#if FZ_ONLY
+    (void)team_lds;
+    constexpr bool by_col = true;
+#else
     const bool by_col = !TEAM && !XCD && NB != 0 && A.by_column != 0;
+#endif
     const int wave = TEAM ? uni_i(wg) : (by_col ? uni_i(tw * P.ny + wg) : uni_i(wg * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6)));
     const bool col_wave = wave < P.ncol && (!by_col || (tw < P.tc && wg < P.ny));
     // NB: neighbour-to-neighbour hand-over instead of the grid barrier.  The unit is the workgroup: one column (teams), or
@@ -58,14 +71,22 @@
     // column][step block: 3 mixing columns, JL, JU][per wave: W][per wave: pivots of the real system][per wave: own Y] (each part
     // present where its bit of A.coef_lds is set; frozen_lds_doubles() on the host computes the same)
     extern __shared__ double dyn_lds[];
+#if FZ_ONLY
+    constexpr bool w_in_lds = true, step_in_lds = true, piv_in_lds = true;
+#else
     const bool w_in_lds = COEF_LDS && (A.coef_lds & 2) != 0;
     const bool step_in_lds = COEF_LDS && by_col && (A.coef_lds & 4) != 0;
     const bool piv_in_lds = COEF_LDS && by_col && (A.coef_lds & 8) != 0;
+#endif
     // the column's own state from phase to phase (OwnState; bits 16, 32 of A.coef_lds -- the host sets them only on top of the
     // full by-column set 15): Y in LDS, the stage values in registers.  Compiled in where the registers hold it; the piece
     // flavour has the stage values only together with Y (with all three bodies <7, 0, 0, 1, 0> spills a register)
     constexpr bool OWN = COEF_LDS && NK2D_FROZEN_OWN(E, KIND, TEAM, LEAN);
+#if FZ_ONLY
+    constexpr int own_bits = 48;
+#else
     const int own_bits = OWN && by_col ? (A.coef_lds & 48) : 0;
+#endif
     (void)own_bits;
     const int nwv = (int)(blockDim.x >> 6);
     double* my_coef;
@@ -107,18 +128,32 @@
     (void)lds_step;
     // option "frozen_early" (bit 8 of A.coef_lds, set by the host only where the year carries the whole own state, CL 63): the wave
     // forms the norm partial of an update part behind that part's stores and stores it behind the hand-over's flag (LateNorm)
+#if FZ_ONLY
+    LateNorm late = {0.0, nullptr, 1, 0};
+#else
     LateNorm late = {0.0, nullptr, (OWN && by_col && own_bits == 48) ? uni_i(NK2D_FROZEN_EARLY_OF(A.coef_lds)) : 0, 0};
+#endif
     (void)late;
     // option "frozen_stage_exchange" (bit 9 of A.coef_lds, under the same rule): the neighbours exchange the stage values U_i = Y + Z_i,
     // not Z_i and Y (StageXchg).  U and UN lie behind the synchronisation block; their parity is Z's and ZN's (swapZ)
+#if FZ_ONLY
+    constexpr bool XCHG = OWN;
+    constexpr int xchg = 1;
+#else
     constexpr bool XCHG = OWN && NK2D_FROZEN_XCHG(E, KIND, TEAM, PIECES, LEAN);     // (compiled in where it costs no spilled register)
     const int xchg = (XCHG && by_col && own_bits == 48) ? uni_i(NK2D_FROZEN_XCHG_OF(A.coef_lds)) : 0;
+#endif
     double* const xu0 = XCHG ? (double*)((char*)A.arrive + yr_xchg_offset(P.ncol)) : nullptr;
     (void)xchg; (void)xu0;
     // option "frozen_xlane" (bit 10 of A.coef_lds, set by the host only on top of bit 9): the body whose cross-lane moves go through the VALU
+#if FZ_ONLY
+    // the hand-over's poll (bit 11 of A.coef_lds, option "frozen_dedicated" 2): NeighbourSync::wait_one_load() instead of wait()
+    const int poll_one = uni_i((A.coef_lds >> 11) & 1);
+#else
     constexpr bool XLANE = XCHG && NK2D_FROZEN_XLANE(E, KIND, TEAM, PIECES, LEAN);
     const int xlane = (XLANE && xchg) ? uni_i(NK2D_FROZEN_XLANE_OF(A.coef_lds)) : 0;
     (void)xlane;
+#endif
 #define FZ_U (swapZ ? xu0 + 3 * nv : xu0)
 #define FZ_UN (swapZ ? xu0 : xu0 + 3 * nv)
     // first attempt of the year: Z0 = 0, W0 = 0 (radau.py:445-446)
@@ -278,6 +313,13 @@
                     Fin.znext = do_stage ? FZ_ZN : FZ_Z;
                     Fin.x0 = R.x0; Fin.x1 = R.x1; Fin.x2 = R.x2;
                     Fin.nblk_cols = 0;
+#if FZ_ONLY
+                    (void)fac;
+                    if (col_wave) {
+                        const StageXchg XC = {FZ_U, do_stage ? FZ_UN : FZ_U, 0};
+                        newton_fused_body<E, KIND, 0, 1, MPX, 1, FZ_ONLY>(P, FA, wave, lane, &Fin, &L, &own, &late, &XC);
+                    }
+#else
                     if constexpr (TEAM) {
                         if constexpr (LEAN) {
                             if (col_wave && fac)
@@ -317,9 +359,19 @@
                         }
                         if (!taken) { newton_fused_body<E, KIND, 0, 1, MPX, 1>(P, FA, wave, lane, &Fin); FZ_OWN_DEAD() }
                     }
+#endif
                     swapY ^= 1;
                     if (do_stage) swapZ ^= 1;
                 } else {
+#if FZ_ONLY
+                    (void)fac;
+                    if (col_wave) {
+                        // (Z to memory where something reads it from there: the estimate and the end of a step that carries one,
+                        // the caller's commit of the last row)
+                        const StageXchg XC = {FZ_U, (do_stage && do_update) ? FZ_UN : FZ_U, (with_err || last_row) ? 1 : 0};
+                        newton_fused_body<E, KIND, 0, 1, MPX, 0, FZ_ONLY>(P, FA, wave, lane, nullptr, &L, &own, &late, &XC);
+                    }
+#else
                     if constexpr (TEAM) {
                         if constexpr (LEAN) {
                             if (col_wave && fac)
@@ -361,6 +413,7 @@
                         }
                         if (!taken) { newton_fused_body<E, KIND, 0, 1, MPX, 0>(P, FA, wave, lane); FZ_OWN_DEAD() }
                     }
+#endif
                     if (do_stage && do_update) swapZ ^= 1;
                 }
                 src = 1 - src;
@@ -371,7 +424,11 @@
                         if (lane == 0) st_mp<MPX>(late.part, late.acc);
                         late.pending = 0;
                     }
+#if FZ_ONLY
+                    if (!(poll_one ? nbs.wait_one_load() : nbs.wait())) { status = 1; goto finish; }
+#else
                     if (!nbs.wait()) { status = 1; goto finish; }
+#endif
                 } else {
                     FZ_SYNC()
                 }

@@ -32,6 +32,22 @@
 // themselves: NK2D_FROZEN_XLANE_MOVES in nk2d_common.h): all but the piece flavour of the linear-source kind at six levels per
 // lane, where that body beside the others makes the compiler report a spilled register (<6, 0, 0, 1, 0>)
 #define NK2D_FROZEN_XLANE(E, KIND, TEAM, PIECES, LEAN) (NK2D_FROZEN_XCHG(E, KIND, TEAM, PIECES, LEAN) && !((E) == 6 && (KIND) == 0 && (PIECES)))
+// The instantiations of k_frozen_persistent_d (nk2d_frozen_d.hip), the entry that carries the body of the default year alone (CL 959:
+// everything in LDS, the whole own state, "frozen_early", the stage-value exchange, the VALU moves): those NK2D_FROZEN_XLANE names
+// for a wave per column on the full cache
+#define NK2D_FROZEN_DEDICATED(E, KIND, PIECES) NK2D_FROZEN_XLANE(E, KIND, 0, PIECES, 0)
+
+// Option "frozen_dedicated" (0: k_frozen_persistent; 1: the dedicated entry with today's hand-over; 2: with the one-load poll) as in
+// effect in a year: the dedicated entry is taken only where the year would run CL 959 in k_frozen_persistent -- every part of the
+// column in LDS and the own state (`lds_bits` 63, which frozen_lds_shape() grants by column only), and "frozen_early", the stage-value
+// exchange and the VALU moves in effect (each 0 where its instantiation has no body for it) -- and the entry has the instantiation
+static inline int frozen_dedicated(int option, int E, int kind, bool team, bool pieces, bool lean, int lds_bits, int early_bits,
+                                   int stage_exchange_bits, int xlane_bits) {
+    if (option != 1 && option != 2) return 0;
+    if (team || lean || !NK2D_FROZEN_DEDICATED(E, kind, pieces ? 1 : 0)) return 0;
+    if (lds_bits != 63 || early_bits != 1 || stage_exchange_bits != 1 || xlane_bits != 1) return 0;
+    return option;
+}
 
 // what of a context (nk2d_ctx) and its options the cache's arithmetic reads
 struct FrozenPlanIn {

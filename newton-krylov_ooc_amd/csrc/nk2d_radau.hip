@@ -1185,6 +1185,7 @@ int run_replay(Ctl& s, const double* sched, int64_t n, bool check) {
                 if (bad_err >= 0) return err_failure(bad_err);
                 c->frozen_persistent_years++;
                 if (nk2d_frozen_cache_is_lean(c)) c->frozen_lean_years++;
+                if (c->frozen_dedicated_bits != 0) c->frozen_dedicated_years++;     // (the entry with the default year's body alone ran it)
                 // (a file-driven forced module above four levels per lane, or with a thresholded sink: option "frozen_forced" let it in)
                 if (c->kind == 2 && (c->E > 4 || (c->d.sms_nrec > 0 && c->d.sink_thres > 0.0))) c->frozen_forced_years++;
                 // (phosphorus: option "frozen_phosphorus" let it in; of those years, the ones that ran the 256-register flavour)

@@ -252,6 +252,10 @@ class ModuleEngine:
         # the one-launch frozen year's cross-lane moves in the VALU instead of through LDS (csrc/nk2d_common.h: the xl_ helpers)
         if "NK2D_FROZEN_XLANE" in os.environ:
             self.set_option("frozen_xlane", float(os.environ["NK2D_FROZEN_XLANE"]))
+        # the one-launch frozen year in the kernel that carries the default year's body alone: 0 off, 1 on, 2 with the one-load poll
+        # (csrc/nk2d_frozen_d.hip), read at every frozen year
+        if "NK2D_FROZEN_DEDICATED" in os.environ:
+            self.set_option("frozen_dedicated", float(os.environ["NK2D_FROZEN_DEDICATED"]))
         # the command-stream year's cross-lane moves at distances 1 and 32, and its wave sums, in the VALU (csrc/nk2d_stream.hip),
         # read at every start of the resident kernel
         if "NK2D_STREAM_XLANE" in os.environ:
