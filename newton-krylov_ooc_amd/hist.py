@@ -139,6 +139,101 @@ def tracer_var_attrs(attrs, tname, label="", unit=None):
     return var_attrs
 
 
+# ---- the history block: every field of the file in the file's byte order, in one array -------------
+# The hand-over format for a producer that forms the fields where the samples are: per variable samples, time_mean, time_anom,
+# time_std, time_delta, depth_int, ypos_mean, depth_ypos_int, then vert_mixing_coeff, all big-endian doubles.  pack_fields_host
+# builds it on the host with every sum in the order of its index; write_hist_file assigns its variables from views of a block.
+FIELD_SUFFIXES = ("", "_time_mean", "_time_anom", "_time_std", "_time_delta", "_depth_int", "_ypos_mean", "_depth_ypos_int")
+
+
+def fields_block_layout(n, nvar, nz, ny):
+    """the block's layout in doubles: {"var_len", "len", "fields": {suffix: (offset inside a variable, shape)},
+    "vert_mixing_coeff": (offset, shape)}; variable v starts at v * var_len"""
+    shapes = ((n, nz, ny), (nz, ny), (n, nz, ny), (nz, ny), (nz, ny), (n, ny), (n, nz), (n,))
+    fields, off = {}, 0
+    for suffix, shape in zip(FIELD_SUFFIXES, shapes):
+        fields[suffix] = (off, shape)
+        off += int(np.prod(shape))
+    vmix_shape = (n, nz + 1, ny)
+    return {"var_len": off, "len": nvar * off + int(np.prod(vmix_shape)), "fields": fields,
+            "vert_mixing_coeff": (nvar * off, vmix_shape)}
+
+
+class FieldsBlock:
+    """A history block with named big-endian views.  Indexing (`block[:, ind]`, `block[-1, 0]`) and `shape` are those of the
+    samples [n, nvar, nz, ny], so that what reads a history's samples reads a block the same way."""
+
+    def __init__(self, block, n, nvar, nz, ny):
+        self.layout = fields_block_layout(n, nvar, nz, ny)
+        self.block = np.asarray(block).view(">f8").reshape(-1)
+        if self.block.size != self.layout["len"]:
+            raise ValueError(f"history block of {self.block.size} doubles, the layout has {self.layout['len']}")
+        self.n, self.nvar, self.nz, self.ny = n, nvar, nz, ny
+        var_len = self.layout["var_len"]
+        self.samples = np.lib.stride_tricks.as_strided(
+            self.block, shape=(n, nvar, nz, ny), strides=(8 * nz * ny, 8 * var_len, 8 * ny, 8), writeable=False)
+        self.shape = self.samples.shape
+
+    def field(self, var, suffix):
+        """view of one field of variable `var` (suffix as in the file: "", "_time_mean", ...)"""
+        off, shape = self.layout["fields"][suffix]
+        start = var * self.layout["var_len"] + off
+        return self.block[start:start + int(np.prod(shape))].reshape(shape)
+
+    @property
+    def vert_mixing_coeff(self):
+        off, shape = self.layout["vert_mixing_coeff"]
+        return self.block[off:off + int(np.prod(shape))].reshape(shape)
+
+    def __getitem__(self, key):
+        return self.samples[key]
+
+    def __len__(self):
+        return self.n
+
+    def __array__(self, dtype=None, copy=None):
+        return np.array(self.samples, dtype=dtype)
+
+
+def pack_fields_host(grid, hist, vmix_coeff):
+    """The history block of samples `hist` [n, nvar, nz, ny] (any tracer-like variable already among them) and mixing coefficients
+    `vmix_coeff` [n, nz-1, ny]: every sum from 0 in the order of
+    its index (time, depth, ypos), every product rounded before it is added.  The reference of the tests and
+    the host's way to the same file."""
+    hist = np.asarray(hist, dtype=np.float64)
+    n, nvar, nz, ny = hist.shape
+    depth, ypos = grid.depth, grid.ypos
+    out = FieldsBlock(np.empty(fields_block_layout(n, nvar, nz, ny)["len"], dtype=">f8"), n, nvar, nz, ny)
+    weights = time_mean_weights(n)
+    yspan = ypos.edges.max() - ypos.edges.min()
+    for var in range(nvar):
+        vals = hist[:, var]
+        mean = np.zeros((nz, ny))
+        for i in range(n):
+            mean = mean + weights[i] * vals[i]
+        anom = vals - mean
+        sumsq = np.zeros((nz, ny))
+        for i in range(n):
+            sumsq = sumsq + weights[i] * (anom[i] * anom[i])
+        depth_int = np.zeros((n, ny))
+        for k in range(nz):
+            depth_int = depth_int + depth.delta[k] * vals[:, k]
+        ypos_int = np.zeros((n, nz))
+        for j in range(ny):
+            ypos_int = ypos_int + ypos.delta[j] * vals[:, :, j]
+        depth_ypos_int = np.zeros(n)
+        for k in range(nz):
+            depth_ypos_int = depth_ypos_int + depth.delta[k] * ypos_int[:, k]
+        for suffix, field in zip(FIELD_SUFFIXES, (vals, mean, anom, np.sqrt(sumsq), vals[-1] - vals[0], depth_int,
+                                                  ypos_int / yspan, depth_ypos_int)):
+            out.field(var, suffix)[...] = field
+    vmix = out.vert_mixing_coeff
+    vmix[:, 1:-1, :] = np.asarray(vmix_coeff) * depth.delta_mid[:, np.newaxis]
+    vmix[:, 0, :] = vmix[:, 1, :]
+    vmix[:, -1, :] = vmix[:, -2, :]
+    return out
+
+
 class HistWriter:
     """History files are written on a background thread: a file is 423 MB at 416 x 416 (the 61 samples of every tracer,
     their anomalies, the mixing coefficient), a second of reductions and big-endian conversion that nothing on the Newton
@@ -146,7 +241,7 @@ class HistWriter:
     for the statistics) is served from the record kept in memory.  Everything that touches a history file BY NAME goes
     through here: `wait` before reading, `remove` / `rename` instead of os.remove / os.rename."""
 
-    KEEP = 3      # records kept in memory (about 170 MB each at 416 x 416 with two tracers)
+    KEEP = 3      # records kept in memory (about 170 MB each at 416 x 416 with two tracers; a FieldsBlock is the whole block, 2.4 times that)
 
     def __init__(self):
         self._pool = None
@@ -264,7 +359,10 @@ def _write_then_rename(fname, grid, time, module_hists, vmix_samples, stamp):
 def write_hist_file(fname, grid, time, module_hists, vmix_coeff, stamp=None):
     """module_hists: list of (tracer metadata dict name -> attrs, hist [ntime, tc, nz, ny]);
     vmix_coeff: the (nz-1, ny) mixing coefficient / dz_mid at every time [ntime, nz-1, ny], or a function of t returning one;
-    stamp: the history attribute (made by the caller when the file is written later than it is asked for)"""
+    stamp: the history attribute (made by the caller when the file is written later than it is asked for).
+    A `hist` that is a FieldsBlock (pack_fields_host) carries its variables' fields in the
+    file's byte order: they are assigned from its views, nothing is reduced or converted; `vmix_coeff` None then takes
+    vert_mixing_coeff from the first block."""
     depth, ypos = grid.depth, grid.ypos
     dname, yname = depth.axisname, ypos.axisname
     dedge, yedge = depth.dump_names["edges"], ypos.dump_names["edges"]
@@ -330,15 +428,23 @@ def write_hist_file(fname, grid, time, module_hists, vmix_coeff, stamp=None):
         fptr.variables["horiz_mixing_coeff"][:] = hmix
         bld = np.stack([bldepth(grid, t) for t in time])
         fptr.variables["bldepth"][:] = bld
-        vmix = np.empty((ntime, len(depth) + 1, len(ypos)))
-        for ind, t in enumerate(time):
-            coeff = vmix_coeff(t) if callable(vmix_coeff) else vmix_coeff[ind]
-            vmix[ind, 1:-1, :] = coeff * depth.delta_mid[:, np.newaxis]
-        vmix[:, 0, :] = vmix[:, 1, :]
-        vmix[:, -1, :] = vmix[:, -2, :]
+        if vmix_coeff is None:
+            vmix = next(hist for _, hist in module_hists if isinstance(hist, FieldsBlock)).vert_mixing_coeff
+        else:
+            vmix = np.empty((ntime, len(depth) + 1, len(ypos)))
+            for ind, t in enumerate(time):
+                coeff = vmix_coeff(t) if callable(vmix_coeff) else vmix_coeff[ind]
+                vmix[ind, 1:-1, :] = coeff * depth.delta_mid[:, np.newaxis]
+            vmix[:, 0, :] = vmix[:, 1, :]
+            vmix[:, -1, :] = vmix[:, -2, :]
         fptr.variables["vert_mixing_coeff"][:] = vmix
         yspan = ypos.edges.max() - ypos.edges.min()
         for tracers, hist in module_hists:
+            if isinstance(hist, FieldsBlock):
+                for ind, tname in enumerate(tracers):
+                    for suffix in FIELD_SUFFIXES:
+                        fptr.variables[tname + suffix][:] = hist.field(ind, suffix)
+                continue
             for ind, tname in enumerate(tracers):
                 vals = hist[:, ind]                       # (time, depth, ypos)
                 mean = np.einsum("i,i...", weights, vals)
